@@ -30,6 +30,11 @@ The timed region is exactly what the contract says: W untimed steps, then K time
 front of the warm-up, default 0; `steady_state` on the JSON line is a separate, later measurement of 200 more steps - a 1000-step
 loop spends 95 % of its time at clocks the device only reaches ~50 steps after a graph capture).
 
+--dump-outputs DIR writes what the timed path computed in its last timed step, as its caller would receive it, to DIR/<name>.npy
+(float32, at most 64 MB in all; a fixed, seeded row sample of a larger output): sample / guided mode `x`, the latent (B,1536,1,32);
+train mode `loss` and `params` (every parameter after the update).  Weights, inputs, noise and the host-side draws are seeded, so a
+run with the same arguments repeats its inputs exactly and two builds compare output for output.
+
 Extra objects on the JSON line:
   roofline      dominant kernel: algorithmic FLOPs per launch / average launch duration (hipEvents on the replay
                 stream around every graph replay of the timed region, divided by the steps it holds; the step is one
@@ -236,6 +241,34 @@ def self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs: all .npy files of a run together (every rank's) stay under 64 MB
+DUMP_SEED = 20240607              # the fixed row sample of an output larger than its share
+
+
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs: the arrays the timed path handed its caller after its last timed step, as `path/<name>.npy` in float32
+    (`<name>_rank<r>` with more than one rank).  An array larger than its share of DUMP_BYTES keeps a fixed, seeded sample of its rows
+    (leading dimension, in index order): the same rows on every run, so that two builds compare output for output.  -> {file: note}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget, info = DUMP_BYTES // world, {}
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())          # small ones first: what they leave goes to the large ones
+    for i, (name, t) in enumerate(items):
+        t = t.detach().float().reshape(-1) if t.dim() == 0 else t.detach().float()
+        share = budget // (len(items) - i) - 256                            # (the .npy header)
+        rows, row_bytes = t.shape[0], t[0].numel() * 4
+        keep = max(1, min(rows, share // row_bytes))
+        if keep < rows:
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(DUMP_SEED))[:keep].sort().values
+            t = t[idx.to(t.device)]
+        a = np.ascontiguousarray(t.cpu().numpy())
+        fname = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(path, fname + ".npy"), a)
+        budget -= a.nbytes + 256
+        info[fname] = {"shape": list(a.shape), "rows": "all" if keep == rows else f"{keep} of {rows}, seeded sample (seed {DUMP_SEED})"}
+    return info
+
+
 def timed_region(step, K, W, world, dist, sync):
     """The contract's timing: W untimed steps, then exactly K steps between barrier + device synchronisation on both
     sides; returns the MAX over ranks of the elapsed seconds."""
@@ -379,6 +412,11 @@ def run_train(args, rank, local, world, dev, dist):
     dt = timed_region(step, K, W, world, dist, torch.cuda.synchronize)
     loss = float(last["loss"])
     assert loss == loss, "non-finite training loss"
+    dumped = None
+    if args.dump_outputs:               # the last timed step's loss and the parameters its update left (before the eager split steps below)
+        with torch.no_grad():
+            params = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()])
+        dumped = dump_outputs(args.dump_outputs, {"loss": last["loss"].detach().reshape(1), "params": params}, rank, world)
     direct = training.direct_grad_report(model) if ddp else None   # gradients the backward wrote straight into the reducer's buckets
     # forward / backward / clip+Adam split of one EAGER step (hipEvents on the current stream; rank 0 only reports it).  After a captured
     # run the same three eager steps follow the timed region: issued from Python the step is host-bound, so these are upper bounds of the
@@ -419,6 +457,8 @@ def run_train(args, rank, local, world, dev, dist):
                        "graph_replayed": graph, "ddp_wrapper": ddp, **({"graph_fallback": fallback} if fallback else {}),
                        **({"gradients_written_into_buckets": {"direct": direct[0], "bound": direct[1], "copied_by_the_reducer": direct[2][:24]}} if direct else {})},
             "loss": round(loss, 5), "step_split": split,
+            **({"dumped_outputs": {"dir": args.dump_outputs, "files": dumped, "what": "loss: the last timed step's loss; params: every parameter after "
+                                                                                      "its update, concatenated in named_parameters() order"}} if dumped else {}),
             "roofline": {"bound": "mfma", "achieved": round(value / world * F_TRAIN / 1e12, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
                          "frac": round(value / world * F_TRAIN / PEAK_BF16, 4), "traffic": None,
                          "note": "whole step (~170 launches, the largest 10 % of it: profiles/r06_train_step_split.txt), F_train = 17.7 GFLOP per sample; no single dominant kernel"}}
@@ -440,8 +480,8 @@ def run_guided(args, rank, local, world, dev, dist):
     g = torch.Generator().manual_seed(77)
     parts = {"upper_mask": torch.randn(1, 256, generator=g).to(dev), "hands_mask": None, "lower_mask": torch.randn(1, 256, generator=g).to(dev)}
 
-    def one(tag, wrapper, B, y_extra, coef, noisy, evals, want_steady):
-        """one guided workload -> dict of its numbers (rank 0) or None"""
+    def one(tag, wrapper, B, y_extra, coef, noisy, evals, want_steady, dump=False):
+        """one guided workload -> dict of its numbers (rank 0) or None; dump: write its latent after the last timed step (--dump-outputs)"""
         only = os.environ.get("SYN_BENCH_ONLY")
         if only and only not in tag:
             return {"workload": tag, "guided_clip_steps_per_s": 0.0, "ms_per_step": 0.0, "variants": 0, "reference_evaluation_equivalents_per_s": 0.0, "roofline": None}
@@ -473,8 +513,10 @@ def run_guided(args, rank, local, world, dev, dist):
         sb.set_rng(4321, first_clip=rank * B)
         if os.environ.get("SYN_BENCH_TRACE"):
             torch.cuda.synchronize(); print("[guided] conditioning done", file=sys.stderr, flush=True)
-        dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, noisy, K, W, args.prime, world, dist, dev, want_steady and rank == 0)
+        kept = {} if dump else None
+        dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, noisy, K, W, args.prime, world, dist, dev, want_steady and rank == 0, kept)
         sb.check_sync()
+        dumped = dump_outputs(args.dump_outputs, kept, rank, world) if dump else None
         if rank != 0:
             return None
         value = world * B * K / dt
@@ -490,6 +532,8 @@ def run_guided(args, rank, local, world, dev, dist):
                                     f"{evals}); duration = hipEvents around the replays of the timed region"}}
         if steady_ms is not None:
             out["steady_state_ms_per_step"] = round(steady_ms, 4)
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped, "what": "x: the latent after the last timed step, as the guided loop returns it"}
         # what the per-clip conditioning (outside the timed region: once per clip, all V variants) adds to a whole loop of this sampler
         L = 1000 if noisy else 50
         loop_ms = L * dt / K * 1e3
@@ -503,7 +547,8 @@ def run_guided(args, rank, local, world, dev, dist):
     cfg = guidance.ClassifierFreeSampleModel(model)
     B3 = args.batch or 512
     main = one("configs[3] diffusion_rvqvae_128_hf.yaml shapes: ClassifierFreeSampleModel(scale 2.5) over the h3d-style denoiser, DDPM-1000 steps "
-               "(noise drawn in the epilogue), cond + uncond as one fused batch", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddpm, True, 2, True)
+               "(noise drawn in the epilogue), cond + uncond as one fused batch", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddpm, True, 2, True,
+               bool(args.dump_outputs))
     d50 = one("configs[3], DDIM-50 steps (eta 0)", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddim, False, 2, False)
     B4 = max(1, B3 // 2)
     body = one("configs[4] diffusion_h3d.yaml: TwoClassifierFreeSampleModel_Bodypart (upper + lower prompts, audio scale 1, prompt scale 4), DDIM-50 steps",
@@ -517,7 +562,7 @@ def run_guided(args, rank, local, world, dev, dist):
                        "parallelism": f"clip-sharded x{world}, no collective", "primed_steps": args.prime * LOOP_CH},
             "reference_evaluation_equivalents_per_s": main["reference_evaluation_equivalents_per_s"],
             "roofline": main["roofline"], "steady_state_ms_per_step": main.get("steady_state_ms_per_step"), "per_clip_conditioning": main.get("per_clip_conditioning"),
-            "ddim50": d50, "bodypart_twocfg": body}
+            **({"dumped_outputs": main["dumped_outputs"]} if "dumped_outputs" in main else {}), "ddim50": d50, "bodypart_twocfg": body}
 
 
 def extras(args, local, dev) -> dict:
@@ -528,6 +573,7 @@ def extras(args, local, dev) -> dict:
     out = {}
     sub = argparse.Namespace(**vars(args))
     sub.batch, sub.steps, sub.warmup, sub.prime, sub.force_ddp = None, 20, 10, 0, False
+    sub.dump_outputs = None                                 # (--dump-outputs holds the headline's timed path only)
     torch.cuda.empty_cache()
     try:
         tr = run_train(sub, 0, local, 1, dev, None)
@@ -607,13 +653,23 @@ def main():
                     help="no GPU work: exercises rank start-up, rendezvous (gloo), the barrier / max-over-ranks timing and the JSON line on CPU")
     ap.add_argument("--layer-mode", type=int, default=0, help="0 library's choice (whole-step kernel at the bench batch), 4 / 3 pin the whole-step / small-batch kernel, "
                          "5 the wave-per-sequence kernel, 1 five kernels per block (the restatement the whole-step kernel is checked against)", choices=[0, 1, 3, 4, 5])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step to DIR/<name>.npy (float32, at most 64 MB "
+                         "in all: a fixed, seeded row sample of a larger output); the inputs are the same on every run with the same arguments")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        sys.exit("bench.py: --dump-outputs needs the GPU run (a dry run computes nothing of the hot path)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
+    # the host-side draws of the timed path (the training step's timesteps: numpy's global RNG; DropPath: torch's) are seeded per rank, so that
+    # a run repeats its inputs exactly
+    import numpy as np
+    np.random.seed(rank)
+    torch.manual_seed(rank)
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     dist = None
@@ -662,14 +718,15 @@ def main():
 LOOP_CH = 10          # steps per hipGraph replay of the hook-free stretches of a sampling loop (process.py `_fused`)
 
 
-def timed_loop(pm, sb, coef, noisy, K, W, prime, world, dist, dev, want_steady):
+def timed_loop(pm, sb, coef, noisy, K, W, prime, world, dist, dev, want_steady, keep=None):
     """The loop exactly as SpacedDiffusion.p_sample_loop / ddim_sample_loop run it (process.py `_fused`): the timestep schedule lives
     on the device, hook-free stretches replay a hipGraph of LOOP_CH = 10 steps (one schedule kernel + syn_denoise_steps: 10 step
     kernels, or ONE persistent 10-step launch of k_seq when the latent is in fragment order), the remainder a single-step graph.
     Noise (DDPM) ~ Philox(seed, step = t, global element index), drawn in the epilogue.
     W untimed steps, then exactly K steps between barrier + synchronize on both sides.
     -> (seconds of the K steps (max over ranks), per-step ms of the replays inside the timed region by hipEvents, ms of a
-        LOOP_CH-step replay, per-step ms of 200 further steps - the steady state of a long loop - or None)"""
+        LOOP_CH-step replay, per-step ms of 200 further steps - the steady state of a long loop - or None)
+    keep: a dict that receives the latent after the last timed step as the loop returns it, (B,1536,1,32) fp32 (--dump-outputs)"""
     from syntalker_amd import engine
     CH, MAXS = LOOP_CH, engine.StepGraph.MAX_STEPS
     n_rows = int(coef.shape[0])                             # 1000 (DDPM) or 50 (DDIM-50): rows of the coefficient table = steps of the loop
@@ -725,6 +782,8 @@ def timed_loop(pm, sb, coef, noisy, K, W, prime, world, dist, dev, want_steady):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(sb.x).all(), "non-finite latent after the timed steps"
+    if keep is not None:
+        keep["x"] = sb.read(sb.x)                           # (before the steady-state steps below move it on)
     steady_ms = None
     if want_steady:
         # A 1000-step loop runs ~50 steps after a graph capture at the clocks it then holds (same box: 1.167 ms per step after 5
@@ -773,7 +832,9 @@ def run_sample(args, rank, local, world, dev, dist):
     sb.load_x(x_T)
     coef = engine.posterior_coefs(diff.tables(), dev)
     sb.set_rng(1234, first_clip=rank * B)
-    dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, True, K, W, args.prime, world, dist, dev, rank == 0)
+    kept = {} if args.dump_outputs else None
+    dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, True, K, W, args.prime, world, dist, dev, rank == 0, kept)
+    dumped = dump_outputs(args.dump_outputs, kept, rank, world) if kept is not None else None
     CH = LOOP_CH
 
     if rank == 0:
@@ -869,6 +930,8 @@ def run_sample(args, rank, local, world, dev, dist):
                              "whole_step_frac": round(B / steady_ms * 1e3 * F_STEP / PEAK_BF16, 4),
                              "note": "200 further steps after the timed region (wall clock, this rank): the clocks a 1000-step loop runs at"},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped, "what": "x: the latent after the last timed step, as p_sample_loop returns it"}
         if args.layer_mode == 0 and not args.no_small_batch and world == 1:
             out["small_batch"] = small_batch_probe(pm, coef, dev)
         if not args.no_cpu and world == 1:      # the CPU baseline is a 1-GPU-run item: the other ranks would only wait for it

@@ -2,7 +2,7 @@
 # Build A/B variants of libsyn_hip.so in parallel: scripts/seq_variants.sh name1="-DFOO=1 -DBAR" name2="" ...
 # -> syntalker_amd/csrc/variants/libsyn_<name>.so (git-ignored, travels with gpurun); run with SYN_HIP_LIB=<path>.
 set -uo pipefail
-SRC=/root/repo/syntalker_amd/csrc
+SRC=$(cd "$(dirname "$0")/../syntalker_amd/csrc" && pwd)
 mkdir -p $SRC/variants
 pids=()
 for spec in "$@"; do

@@ -126,3 +126,53 @@ def test_bench_refuses_to_run_the_hot_path_without_a_gpu():
     e = dict(os.environ); e.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1"], capture_output=True, text=True, timeout=240, env=e)
     assert r.returncode != 0 and "no GPU visible" in r.stderr
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_keeps_a_fixed_row_sample_under_64_mb(tmp_path):
+    """--dump-outputs: float32 .npy files, at most 64 MB in all; an output larger than its share keeps the same seeded rows on every call,
+    a small one is written whole."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    x = torch.randn(1024, 1536, 1, 32)                                    # the headline's latent: 201 MB in float32
+    a, b = tmp_path / "a", tmp_path / "b"
+    ia, ib = bench.dump_outputs(str(a), {"x": x}, 0, 1), bench.dump_outputs(str(b), {"x": x.clone()}, 0, 1)
+    assert ia == ib and ia["x"]["shape"][1:] == [1536, 1, 32] and 1 < ia["x"]["shape"][0] < 1024
+    xa = np.load(a / "x.npy")
+    assert xa.dtype == np.float32 and np.array_equal(xa, np.load(b / "x.npy")) and os.path.getsize(a / "x.npy") <= bench.DUMP_BYTES
+    rows = [i for i in range(1024) if any(np.array_equal(x[i].numpy(), r) for r in xa[:3])]
+    assert len(rows) == 3 and rows == sorted(rows)                           # rows of the input, in index order
+    c = tmp_path / "c"
+    info = bench.dump_outputs(str(c), {"loss": torch.tensor(0.25, dtype=torch.float64), "params": torch.randn(29_607_012)}, 0, 1)
+    assert info["loss"]["rows"] == "all" and np.load(c / "loss.npy").tolist() == [0.25]
+    assert sum(os.path.getsize(c / f) for f in os.listdir(c)) <= bench.DUMP_BYTES
+    d = tmp_path / "d"
+    bench.dump_outputs(str(d), {"x": torch.randn(8, 1536, 1, 32)}, 1, 2)   # rank 1 of 2: its own file, half the budget
+    assert os.listdir(d) == ["x_rank1.npy"] and np.load(d / "x_rank1.npy").shape == (8, 1536, 1, 32)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """Two runs with the same arguments: `steps` timed steps (12: ten-step replays and single-step ones), `ms_per_step` on the line, and the same
+    latent after the last timed step, bit for bit."""
+    import numpy as np
+    got = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        e = dict(os.environ); e.pop("WORLD_SIZE", None)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--batch", "64", "--no-extras",
+                            "--no-cpu", "--no-small-batch", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=e)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 12 and out["ms_per_step"] > 0 and len(out["roofline"]["timed_region_replays_ms_per_step"]) == 3
+        assert out["dumped_outputs"]["files"]["x"] == {"shape": [64, 1536, 1, 32], "rows": "all"}
+        got.append(np.load(d / "x.npy"))
+    assert got[0].dtype == np.float32 and np.isfinite(got[0]).all() and np.array_equal(got[0], got[1])

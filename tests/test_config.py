@@ -1,11 +1,11 @@
 """configuration / checkpoint compatibility of the hot path.
 
-CPU part: the reference's own YAML files (read in the build container, where the reference tree exists) select the denoiser class and
-the body-part widths their trainers build; the StepLR policy; the checkpoint format.  GPU part: the `train.py -c <yaml>` loop of
+CPU part: the reference's own YAML files (the keys this package reads, stored as tests/golden/reference_configs.json by
+tests/golden/make_config_golden.py) select the denoiser class and the body-part widths their trainers build; the StepLR policy; the checkpoint format.  GPU part: the `train.py -c <yaml>` loop of
 scripts/train_from_config.py (epochs, per-epoch StepLR, save_checkpoints, resume from a `module.`-prefixed checkpoint) and the
 sampler built from the h3d configuration."""
-import glob
 import importlib.util
+import json
 import os
 
 import pytest
@@ -14,7 +14,7 @@ import torch
 from syntalker_amd import checkpoint, config
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CONFIGS = "/root/reference/configs"
+REF_CONFIGS = os.path.join(REPO, "tests", "golden", "reference_configs.json")
 
 H3D_YAML = ("model: denoiser_h3d\ng_name: MDM\ntrainer: h3d_diffusion_new\nvqvae_type: rvqvae\nvqvae_squeeze_scale: 4\nvqvae_latent_scale: 10.0\n"
             "audio_f: 256\nword_f: 256\npose_length: 128\npre_frames: 4\npose_fps: 30\naudio_rep: onset+amplitude\nbatch_size: 200\nlr_base: 5e-5\n"
@@ -30,14 +30,19 @@ def _driver(name):
     return m
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="the reference's configs exist only in the build container")
-def test_the_references_own_yaml_files_select_class_and_widths():
+def test_the_references_own_yaml_files_select_class_and_widths(tmp_path):
     """train.py:85-94 `getattr(__import__(f"models.{args.model}"), args.g_name)`; diffusion_rvqvae_trainer.py:105-139 /
-    h3d_diffusion_new_trainer.py:104-146 body-part widths."""
+    h3d_diffusion_new_trainer.py:104-146 body-part widths.  Each of the reference's configs/*.yaml, written back out as YAML from
+    its stored keys, goes through `config.load_args` as the file would."""
+    import yaml
+    with open(REF_CONFIGS) as f:
+        configs = json.load(f)
+    assert len(configs) == 6
     seen = {}
-    for path in sorted(glob.glob(os.path.join(REF_CONFIGS, "*.yaml"))):
-        a = config.load_args(path)
-        name = os.path.basename(path)
+    for name, keys in sorted(configs.items()):
+        path = tmp_path / name
+        path.write_text(yaml.safe_dump(keys))
+        a = config.load_args(str(path))
         if a.model in config.MODEL_MODULES:
             cls = config.model_class(a)
             seen[name] = (cls.__module__, cls.__name__, config.body_dims(a), config.is_h3d(a))
