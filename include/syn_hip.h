@@ -610,6 +610,43 @@ int syn_vq_forward_decoder(const syn_vq_model* m, const int32_t* idx, int32_t n_
 int syn_axis_angle_to_rot6d(const float* axis_angle, int64_t n_joints, float* rot6d, void* stream);
 int syn_rot6d_to_axis_angle(const float* rot6d, int64_t n_joints, float* axis_angle, void* stream);
 
+/* ---- TMR encoders (models/temos/motionencoder/actor.py, textencoder/distillbert_actor.py; h3d_diffusion_new_trainer.py:170-176, 370-374) ----
+ * ActorAgnosticEncoder's stack: input Linear (ReLU first for the text encoder's projection), [mu_token; logvar_token; rows] + pe, 4 post-norm
+ * nn.TransformerEncoderLayer (256 wide, 4 heads x 64, FF 1024, erf GELU, LayerNorm eps 1e-5, dropout inactive), keys >= 2 + length masked;
+ * out: mu = final[0], logvar = final[1].  GEMMs on hi + lo bf16 operands, attention on bf16 operands, fp32 residual / LayerNorm / softmax. */
+#define SYN_TMR_D         256
+#define SYN_TMR_LAYERS    4
+#define SYN_TMR_MAX_LEN   254      /* rows per sequence without the two distribution tokens */
+#define SYN_TMR_MAX_FEATS 4096     /* columns of the input Linear */
+#define SYN_TMR_MAX_SEQ   65536
+
+typedef struct syn_tmr_layer {
+    const void*  w_qkv;  const float* b_qkv;      /* packed self_attn.in_proj_weight (768 x 256), in_proj_bias      */
+    const void*  w_out;  const float* b_out;      /* packed self_attn.out_proj (256 x 256), bias                   */
+    const float* ln1_g;  const float* ln1_b;      /* norm1                                                          */
+    const void*  w_fc1;  const float* b_fc1;      /* packed linear1 (1024 x 256), bias                              */
+    const void*  w_fc2;  const float* b_fc2;      /* packed linear2 (256 x 1024), bias                              */
+    const float* ln2_g;  const float* ln2_b;      /* norm2                                                          */
+} syn_tmr_layer;
+
+typedef struct syn_tmr_model {
+    int32_t      nfeats;                          /* columns of the input Linear (623 motion, 768 DistilBERT)       */
+    int32_t      relu_in;                         /* 1: ReLU before the input Linear (projection = ReLU, Linear)    */
+    const void*  w_in;   const float* b_in;       /* packed skel_embedding / projection.1 (256 x nfeats), bias      */
+    const float* mu_token; const float* logvar_token;   /* (256) each                                              */
+    const float* pe;                              /* sequence_pos_encoding.pe: >= max_len + 2 rows of 256           */
+    syn_tmr_layer layer[SYN_TMR_LAYERS];
+} syn_tmr_model;
+
+/* fp32 w [n][k] (nn.Linear layout) -> `out`: hi then lo bf16 MFMA fragments, 2 x n x roundup(k, 32) bf16 (4 n roundup(k, 32) bytes).
+ * n a multiple of 16, 1 <= k <= SYN_TMR_MAX_FEATS.  Once per weight change. */
+int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream);
+/* features fp32 [n_seq][max_len][nfeats] -> mu, logvar fp32 [n_seq][256].  lengths: device int32 [n_seq] valid rows per sequence (clamped to
+ * 0 .. max_len), NULL = all max_len.  workspace: (max_len + 2) n_seq x 7680 bytes (x fp32 256 | qkv bf16 768 | attention fp32 256 |
+ * FF hidden fp32 1024 per row).  1 <= max_len <= SYN_TMR_MAX_LEN, 1 <= n_seq <= SYN_TMR_MAX_SEQ.  22 launches, no allocation, no sync. */
+int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                   float* mu, float* logvar, void* stream);
+
 /* ResidualVQ.forward in eval mode (models/vq/residual_vq.py:91-140 over quantizer.py:62-69,143-171), fp32, 6 layers
  * of 512 codes x 512 dims: x [rows][512] -> q_f32 / q_bf16 [rows][512] (sum of the straight-through outputs), idx
  * [rows][6], sqerr [syn_vq_quantize_groups(rows)][6] (per-group sums of |residual - code|^2: commit loss numerators),

@@ -12,7 +12,8 @@ The reference's data loaders (lmdb caches of BEAT-X / HumanML3D, dataloaders/*.p
 image: without --data the loop trains on synthetic batches of the shapes `_load_data` hands to `_g_training` (x0 (B,1536,1,32) =
 the RVQ-VAE latents / vqvae_latent_scale, audio (B, 68266, 2), word ids (B, 128), seed latents (B, 4, 1536)).
 --data      npz with arrays latent (N,1536,1,32) [already divided by vqvae_latent_scale], audio (N,68266,2), word (N,128), seed (N,4,1536)
-            [, style_feature (N,256) for the h3d configuration]; an epoch walks it in batches of batch_size.
+            [, style_feature (N,256) for the h3d configuration, or tmr_tar_pose (N,128,623) (+ prompt_text (N,), tar_id (N,)): the batch's
+            style_feature from the TMR encoders, h3d_diffusion_new_trainer.py:370-374]; an epoch walks it in batches of batch_size.
 --resume    a checkpoint of the reference's format; keys with nn.DataParallel's `module.` prefix are accepted.
 --graph     replay the whole step from one hipGraph (training.GraphedTrainStep; static batch shape).
 With more than one rank (torchrun) the model is wrapped by training.make_ddp and every rank trains on its own batches: with --data the
@@ -38,7 +39,29 @@ def synthetic_batch(args, B, seed, dev):
     return synth.synth_latent(B, seed=seed, name="x0").to(dev), synth.to_device(y, dev)
 
 
-def batches_from(npz, args, B, dev, rank=0, world=1, epoch=0, seed=0):
+class TmrStyle:
+    """style_feature of an h3d batch from its motion (h3d_diffusion_new_trainer.py:370-374): the TMR motion encoder's mean of `tmr_tar_pose`;
+    with text_sample_stride > 0 and `prompt_text` / `tar_id` in the file, every stride-th row with tar_id == 99 takes the text encoder's mean
+    of its prompt instead.  Both encoders from tmr.build_encoders (tmr_base_path, tmr_text_model_path), on the HIP stack kernel."""
+
+    def __init__(self, args, dev, z):
+        from syntalker_amd import tmr
+        self.stride = int(getattr(args, "text_sample_stride", 0) or 0)
+        use_text = self.stride > 0 and "prompt_text" in z and "tar_id" in z
+        self.motion, self.text = tmr.build_encoders(args, dev, text=use_text)
+
+    @torch.no_grad()
+    def __call__(self, z, ix, dev):
+        style = self.motion(torch.from_numpy(z["tmr_tar_pose"][ix]).float().to(dev)).loc
+        if self.text is not None:
+            use = np.where(z["tar_id"][ix].reshape(len(ix), -1)[:, 0] == 99)[0][::self.stride]
+            if len(use):
+                rows = torch.from_numpy(use).to(dev)
+                style[rows] = self.text([str(t) for t in z["prompt_text"][ix]]).loc[rows]
+        return style
+
+
+def batches_from(npz, args, B, dev, rank=0, world=1, epoch=0, seed=0, style=None):
     """One epoch of THIS rank's batches (train.py:54-61: DataLoader(batch_size, drop_last=True) over DistributedSampler(train_data) under DDP,
     shuffle=True otherwise; the sampler is re-seeded per epoch, train.py:277): `sharding.epoch_batches` deals the epoch's permutation
     round-robin over the ranks, so an N-rank run trains on N disjoint batches per step - a global batch of N x B."""
@@ -50,6 +73,8 @@ def batches_from(npz, args, B, dev, rank=0, world=1, epoch=0, seed=0):
         y = {"audio": torch.from_numpy(z["audio"][ix]).float(), "word": torch.from_numpy(z["word"][ix]).long(),
              "seed": torch.from_numpy(z["seed"][ix]).float(), "mask": torch.ones(B, 1, 1, 32, dtype=torch.bool),
              "style_feature": torch.from_numpy(z["style_feature"][ix]).float() if "style_feature" in z else torch.zeros(B, 512)}
+        if style is not None and "style_feature" not in z and "tmr_tar_pose" in z:
+            y["style_feature"] = style(z, ix, dev)
         yield torch.from_numpy(z["latent"][ix]).float().to(dev), synth.to_device(y, dev)
 
 
@@ -105,10 +130,18 @@ def main(argv=None) -> dict:
     os.makedirs(a.out, exist_ok=True)
     watch = {n: p.detach().clone() for n, p in t.model.named_parameters() if n.split(".")[0] in ("uncon_text_embeddings", "uncon_audio_embeddings", "embed_style")}
     step_fn, log, saved = None, [], []
+    style = None
+    if a.data and config.is_h3d(args):
+        with np.load(a.data) as z:
+            if "tmr_tar_pose" in z.files and "style_feature" not in z.files:
+                style = TmrStyle(args, dev, z)
+                if rank == 0:
+                    print("style_feature: TMR motion encoder on tmr_tar_pose" + (" + text encoder on prompt_text" if style.text is not None else ""),
+                          flush=True)
     for epoch in range(epochs + 1):                                           # train.py:270: range(args.epochs + 1), the last one only saves
         if epoch != epochs:
             net.train()
-            it = batches_from(a.data, args, B, dev, rank, world, epoch, a.seed) if a.data else (synthetic_batch(args, B, 1000 * epoch + s + 100000 * rank, dev)
+            it = batches_from(a.data, args, B, dev, rank, world, epoch, a.seed, style) if a.data else (synthetic_batch(args, B, 1000 * epoch + s + 100000 * rank, dev)
                                                                      for s in range(a.steps_per_epoch))
             t0, losses = time.time(), []
             for x0, y in it:

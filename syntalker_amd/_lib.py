@@ -25,7 +25,8 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_conv1d_first_fwd_stats", "syn_test_mfma_rate", "syn_conv1d_train_dgrad_sum", "syn_conv1d_first_fwd2", "syn_conv1d_first_wgrad_bn",
            "syn_bn_bwd_stats", "syn_train_stack_fwd", "syn_train_stack_bwd", "syn_train_stack_wgrad",
            "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
-           "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair")
+           "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
+           "syn_tmr_pack_weight", "syn_tmr_encode")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -120,6 +121,21 @@ class SynVqConv(C.Structure):
 class SynVqModel(C.Structure):
     _fields_ = [("pose_dim", i32), ("reserved", i32), ("enc", SynVqConv * 16), ("dec", SynVqConv * 17),
                 ("codebooks", vp), ("codebooks_t", vp), ("code_sq", vp)]
+
+
+SYN_TMR_LAYERS = 4
+SYN_TMR_MAX_LEN = 254       # include/syn_hip.h: rows per sequence without the two distribution tokens
+SYN_TMR_MAX_FEATS = 4096
+
+
+class SynTmrLayer(C.Structure):
+    _fields_ = [("w_qkv", vp), ("b_qkv", vp), ("w_out", vp), ("b_out", vp), ("ln1_g", vp), ("ln1_b", vp),
+                ("w_fc1", vp), ("b_fc1", vp), ("w_fc2", vp), ("b_fc2", vp), ("ln2_g", vp), ("ln2_b", vp)]
+
+
+class SynTmrModel(C.Structure):
+    _fields_ = [("nfeats", i32), ("relu_in", i32), ("w_in", vp), ("b_in", vp), ("mu_token", vp), ("logvar_token", vp), ("pe", vp),
+                ("layer", SynTmrLayer * SYN_TMR_LAYERS)]
 
 
 class SynHipError(RuntimeError):
@@ -246,6 +262,8 @@ def load():
     lib.syn_vq_map2latent.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, vp, vp, vp]
     lib.syn_vq_latent2origin.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.syn_vq_forward_decoder.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, i32, vp, vp, vp]
+    lib.syn_tmr_pack_weight.argtypes = [vp, i32, i32, vp, vp]
+    lib.syn_tmr_encode.argtypes = [C.POINTER(SynTmrModel), vp, i32, i32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes"):

@@ -1685,6 +1685,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_glue.inc"
 #include "syn_rvq.inc"
 #include "syn_pose.inc"
+#include "syn_tmr.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2142,6 +2143,14 @@ int syn_rot6d_to_axis_angle(const float* rot6d, int64_t n_joints, float* axis_an
     hipLaunchKernelGGL(pose::k_rot6d_to_aa, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rot6d, (long)n_joints, axis_angle);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail("k_rot6d_to_aa launch", e);
+}
+
+// TMR encoders (syn_tmr.inc)
+int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream) { return tmr::pack_weight(w, n, k, out, stream); }
+
+int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                   float* mu, float* logvar, void* stream) {
+    return tmr::encode(m, features, n_seq, max_len, lengths, workspace, mu, logvar, stream);
 }
 
 int syn_test_gemm(const void* x_bf16, const void* w_packed, const float* bias, int32_t m_rows, int32_t n, int32_t k,

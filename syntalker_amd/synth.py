@@ -198,3 +198,44 @@ def synth_pose_clip(batch: int, n_pose: int, seed: int = 27) -> dict:
     pose = 0.5 * torch.randn(batch, n_pose, 165, generator=g)
     pose[:, ::7, 9:12] = 0.0
     return {"pose": pose, "trans_v": 0.05 * torch.randn(batch, n_pose, 3, generator=g)}
+
+
+# ---- TMR encoders (h3d_diffusion_new_trainer.py:168-176): weights, motion features, an offline DistilBERT ------------------------------
+TMR_NFEATS = 623
+TMR_PROMPTS = ["a person waves the right hand", "someone walks forward slowly and then turns around to look back",
+               "a man jumps"]
+TMR_PROMPT_ONE = "a person raises both arms above the head"
+_TMR_WORDS = ("a person waves the right left hand someone walks forward slowly and then turns around to look back man jumps raises both "
+              "arms above head walk run sit stand up down kick dance").split()
+
+
+def synth_tmr_state_dict(module: torch.nn.Module, seed: int = 31) -> dict:
+    """The seeded weights of a TMR encoder with the reference's keys (every entry but the positional table: LayerNorm gamma = 1 + 0.1 N(0,1),
+    beta / biases / distribution tokens 0.05 N(0,1), matrices N(0, 1/fan_in)); `module` supplies the keys and shapes."""
+    sd = {k: torch.zeros_like(v) for k, v in module.state_dict().items()}
+    for k, v in module.state_dict().items():
+        if synth_tensor(k, v.shape, seed) is None:
+            sd[k] = v.detach().clone()
+    return synth_fill_(sd, seed)
+
+
+def synth_tmr_motion(batch: int, frames: int = 128, seed: int = 32) -> torch.Tensor:
+    """(B, frames, 623) stand-in for the h3d loader's `tmr_tar_pose` (normalised HumanML3D features: unit scale)."""
+    return torch.randn(batch, frames, TMR_NFEATS, generator=_gen("tmr_motion", seed))
+
+
+def synth_tmr_text_model(path: str, seed: int = 33, layers: int = 2):
+    """Write an offline DistilBERT directory (synthetic vocab.txt, 768-wide config of `layers` layers, seeded weights, tokenizer files) that
+    `AutoTokenizer / AutoModel.from_pretrained(path)` read without a network."""
+    import os
+    from transformers import DistilBertConfig, DistilBertModel, DistilBertTokenizer
+    os.makedirs(path, exist_ok=True)
+    vocab = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + sorted(set(_TMR_WORDS))
+    with open(os.path.join(path, "vocab.txt"), "w") as f:
+        f.write("\n".join(vocab) + "\n")
+    cfg = DistilBertConfig(vocab_size=len(vocab), dim=768, n_layers=layers, n_heads=12, hidden_dim=3072, max_position_embeddings=512)
+    model = DistilBertModel(cfg)
+    synth_fill_(model, seed)
+    model.save_pretrained(path)
+    DistilBertTokenizer(os.path.join(path, "vocab.txt"), do_lower_case=True).save_pretrained(path)
+    return path
