@@ -150,48 +150,43 @@ class MDM(nn.Module):
         elif self.use_motionclip:
             self.input_process3 = nn.Linear(self.latent_dim + 512, self.latent_dim)
         self.mix_audio_text = nn.Linear(audio_f + word_f, 256)
-        self._packed, self._packed_key = None, None
-        self._bufs, self._cond_entry = {}, None
         self.m_tile = 0
         self.layer_mode = 0            # syn_step.reserved: 0 library's choice (small-batch kernel for few sequences, else the
                                        # whole-step kernel); 4 / 3 / 5 pin one of them; 1: five kernels per block (bitwise cross-check, h8 tap)
         self.differentiable_eval = False   # eval() + autograd on: take the differentiable path (gradient tests)
 
-    def __getstate__(self):
-        """copy.deepcopy(model) (an EMA copy) and torch.save(model) take the module as nn.Module defines it - parameters, buffers, attributes - and none
-        of the device-side caches derived from them (ctypes structs of raw pointers into THIS module's packed tensors): the copy builds its own."""
-        st = self.__dict__.copy()
-        st["_packed"], st["_packed_key"], st["_bufs"], st["_cond_entry"] = None, None, {}, None
-        for k in [k for k in st if k.startswith("_syn_") or k in ("_ident", "_graphs")]:          # (`_graphs`: the captured loops of process._fused)
-            del st[k]
-        return st
+    __getstate__ = engine.drop_caches         # (an EMA copy, torch.save: without the `_syn_*` caches, created lazily by their readers)
 
     # ---- engine plumbing ----------------------------------------------------------------------
     @property
     def uses_style(self):
         return self.variant == "h3d" or self.use_motionclip
 
-    def _weights_key(self):
-        return (engine.raw_write_epoch(),) + tuple((t.data_ptr(), t._version) for t in self.state_dict(keep_vars=True).values())
+    @property
+    def _packed(self):
+        """The packed weights as last built, None before the first `packed()` (and in a copy, which leaves the `_syn_*` caches behind)."""
+        return self.__dict__.get("_syn_packed")
 
     def packed(self) -> engine.PackedModel:
-        """Folded/packed weights, rebuilt when any parameter was modified in place or moved."""
-        key = self._weights_key()
-        if self._packed is None or key != self._packed_key:
-            sd = {k: v.detach() for k, v in self.state_dict(keep_vars=True).items()}
-            self._packed, self._packed_key = engine.PackedModel(sd, self.variant, self.uses_style), key
-            self._cond_entry = None
-        return self._packed
+        """Folded/packed weights, rebuilt when any parameter or buffer was written or moved (`engine.weights_key`)."""
+        sd = self.state_dict(keep_vars=True)
+        key = engine.weights_key(sd.values())
+        if self.__dict__.get("_syn_packed_key") != key:
+            self._syn_packed = engine.PackedModel({k: v.detach() for k, v in sd.items()}, self.variant, self.uses_style)
+            self._syn_packed_key = key
+            self._syn_cond_entry = None
+        return self._syn_packed
 
     def step_buffers(self, B, V=1, want_x0=False) -> engine.StepBuffers:
         """The device buffers of a loop over B clips x V variants (cached).  (Named so that `nn.Module.buffers()` stays what PyTorch's wrappers -
         nn.DataParallel.forward, the reference's default wrap, train.py:94 - expect it to be.)"""
         k = (B, V, want_x0, self.m_tile, self.layer_mode)
-        if k not in self._bufs:
-            if len(self._bufs) > 4:
-                self._bufs.clear()
-            self._bufs[k] = engine.StepBuffers(B, V, next(self.parameters()).device, want_x0, self.m_tile, self.layer_mode)
-        return self._bufs[k]
+        bufs = self.__dict__.setdefault("_syn_bufs", {})
+        if k not in bufs:
+            if len(bufs) > 4:
+                bufs.clear()
+            bufs[k] = engine.StepBuffers(B, V, next(self.parameters()).device, want_x0, self.m_tile, self.layer_mode)
+        return bufs[k]
 
     def variant_conds(self, y: dict, variants) -> torch.Tensor:
         """cond rows for a list of (uncond, uncond_audio, style_override) variants -> (V, B, 32, 512).
@@ -201,7 +196,7 @@ class MDM(nn.Module):
         tens = [y.get(k) for k in ("audio", "word", "seed", "style_feature")]
         sig = tuple((id(t), t._version) if torch.is_tensor(t) else None for t in tens)
         vkey = tuple((bool(u), bool(ua), None if st is None else (id(st), st._version)) for u, ua, st in variants)
-        ent = self._cond_entry
+        ent = self.__dict__.get("_syn_cond_entry")
         if ent is not None and ent[0] == (sig, vkey, id(pm)):
             return ent[2]
         frame_cache, rows = {}, []
@@ -209,7 +204,7 @@ class MDM(nn.Module):
             yy = y if style is None else dict(y, style_feature=style)
             rows.append(pm.conditioner.cond(yy, uncond, uncond_audio, frame_cache))
         cond = torch.stack(rows, 0).contiguous()
-        self._cond_entry = ((sig, vkey, id(pm)), (tens, [v[2] for v in variants]), cond)   # keep refs: ids stay unique
+        self._syn_cond_entry = ((sig, vkey, id(pm)), (tens, [v[2] for v in variants]), cond)   # keep refs: ids stay unique
         return cond
 
     def own_variant(self, y: dict):
@@ -251,9 +246,11 @@ class MDM(nn.Module):
             return sb.read(sb.x)
 
     def _identity(self):
-        if getattr(self, "_ident", None) is None or self._ident.device != next(self.parameters()).device:
-            self._ident = engine.identity_coefs(next(self.parameters()).device)
-        return self._ident
+        dev = next(self.parameters()).device
+        ident = self.__dict__.get("_syn_ident")
+        if ident is None or ident.device != dev:
+            ident = self._syn_ident = engine.identity_coefs(dev)
+        return ident
 
 
 MDM_RVQ = MDM      # the name BASELINE.json's north_star uses for this class

@@ -24,20 +24,17 @@ from .conditioning import ClipConditioner, fold_input_stage, rotary_tables, time
 T, CH, D, FF, LAYERS = 32, 1536, 512, 1024, 8
 
 
-# Parameters and buffers are also written where PyTorch's in-place version counters do not see it: `ClipAdam`'s update and the BatchNorm running
-# statistics go through raw pointers, and a replayed `GraphedTrainStep` is one opaque launch.  Every such writer calls `note_raw_write()`; the caches of
-# derived weights (`MDM.packed()`, `RVQVAE.packed()`) key on this count next to the tensors' versions, so the first sampling call after any training
-# step folds and packs the weights again (the reference's trainer samples between epochs: diffusion_rvqvae_trainer.py `val` / `test`).
-_raw_writes = 0
+def weights_key(tensors) -> tuple:
+    """The staleness key of every cache derived from module weights (folded / packed weights, fragment sets, tables): each tensor's address and
+    in-place version.  The writers PyTorch cannot see - `ClipAdam`'s update, a replayed `GraphedTrainStep`, the BatchNorm finalize kernels of a
+    training forward - write through raw pointers and bump the versions of exactly what they wrote (`torch.autograd.graph.increment_version`)."""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
 
 
-def note_raw_write():
-    global _raw_writes
-    _raw_writes += 1
-
-
-def raw_write_epoch() -> int:
-    return _raw_writes
+def drop_caches(module) -> dict:
+    """`__getstate__` of a module whose derived device-side state lives in `_syn_*` attributes (ctypes structs of raw pointers into ITS packed
+    tensors, captured graphs): copy.deepcopy and torch.save take the module as nn.Module defines it, and the copy builds its own caches."""
+    return {k: v for k, v in module.__dict__.items() if not k.startswith("_syn_")}
 
 
 def _require_cuda(t: torch.Tensor, what: str):

@@ -247,7 +247,7 @@ class ClipAdam(torch.optim.Optimizer):
                                            0.0 if lr_dev is not None else float(lr), b1, b2, step.data_ptr(), scal[gi].data_ptr(), st), "syn_opt_scalars")
             for L in lists:
                 _lib.check(lib.syn_opt_adam(C.byref(L), scal[gi].data_ptr(), b1, b2, group["eps"], group["weight_decay"], st), "syn_opt_adam")
-        engine.note_raw_write()                                          # (the parameters moved and their version counters did not)
+        torch.autograd.graph.increment_version([p for _, ps, *_ in groups for p in ps])    # (written through pointers: `engine.weights_key`)
         return loss
 
 
@@ -275,8 +275,8 @@ def train_step(model, diffusion, sampler, optimizer, x0, model_kwargs, grad_norm
 class GraphedTrainStep:
     """`train_step` captured once in a hipGraph and replayed.  The step is ~1 000 kernel launches long and host-bound
     when issued from Python (device time 15 ms, wall 17-21 ms at 32 clips); a replay costs the device time (15.5 ms).
-    Static shapes: every call must bring tensors of the shapes seen at construction.  The optimizer must be constructed
-    with ``capturable=True``.  With DDP: wrap with ``make_ddp(..., capturable=True)`` inside ``torch.cuda.stream(s)``,
+    Static shapes: every call must bring tensors of the shapes seen at construction.  A ``torch.optim.Adam`` must be constructed
+    with ``capturable=True`` (`ClipAdam` is capturable as it is).  With DDP: wrap with ``make_ddp(..., capturable=True)`` inside ``torch.cuda.stream(s)``,
     pass ``stream=s`` and ``warmup=11`` (DDP needs that many eager iterations before a capture), and set
     ``TORCH_NCCL_ASYNC_ERROR_HANDLING=0`` before ``init_process_group`` - the bucketed all-reduces are then nodes of the
     graph (`scripts/bench_train_ddp.py`; checked with one rank over RCCL: 22.6 ms eager -> 18.0 ms replayed).
@@ -296,6 +296,7 @@ class GraphedTrainStep:
         engine._require_cuda(x0, "x0")
         _check_clip(optimizer, grad_norm)
         self.model, self.opt, self.grad_norm, self.diffusion = model, optimizer, grad_norm, diffusion
+        self._written = list(model.parameters()) + list(model.buffers())    # what a replay writes: the update, the BatchNorm statistics
         self.wrapped = diffusion._wrap_model(model)          # its timestep map is uploaded once, outside the capture
         self.x0 = x0.detach().clone()
         self.t = torch.zeros(x0.shape[0], dtype=torch.long, device=x0.device)
@@ -405,7 +406,7 @@ class GraphedTrainStep:
             if torch.is_tensor(v):
                 self.y[k].copy_(v)
         self.graph.replay()
-        engine.note_raw_write()                                          # (parameters, BatchNorm statistics: one opaque launch to the version counters)
+        torch.autograd.graph.increment_version(self._written)           # (one opaque launch: `engine.weights_key`)
         return self.loss.clone()        # (stream-ordered copy: the static tensor is overwritten by the next replay)
 
     def close(self):

@@ -367,7 +367,7 @@ class GaussianDiffusion:
             fused_rng = noisy and step_noise is None     # noise drawn inside the output GEMM's epilogue
             if fused_rng:
                 sb.set_rng(seed, first_clip)
-            graphs = mdm.__dict__.setdefault("_graphs", {})
+            graphs = mdm.__dict__.setdefault("_syn_graphs", {})
 
             def graph_of(steps):
                 gkey = ("graph", id(pm), id(sb), coef.data_ptr(), noisy, fused_rng, steps)

@@ -85,13 +85,9 @@ class RVQVAE(nn.Module):
             _register(self, key + ".bias", torch.zeros(cout))
         for q in range(NUM_Q):
             _register(self, f"quantizer.layers.{q}.codebook", torch.zeros(nb_code, code_dim), buffer=True)
-        self._packed = None
         self.eval()
 
-    def __getstate__(self):
-        st = self.__dict__.copy()               # (deepcopy / torch.save: without the packed copy - ctypes pointers into this module's tensors)
-        st["_packed"] = None
-        return st
+    __getstate__ = engine.drop_caches         # (deepcopy / torch.save: without the packed copy - ctypes pointers into this module's tensors)
 
     def train(self, mode: bool = True):
         if mode:
@@ -101,11 +97,11 @@ class RVQVAE(nn.Module):
     # ---- device-side parameters ----------------------------------------------------------------------------------
     def packed(self):
         """syn_vq_model of this module: fragment-packed conv weights, padded biases, codebook views.  Rebuilt when a
-        parameter changes (version counters) or moves."""
-        tensors = list(self.parameters()) + list(self.buffers())
-        ver = (engine.raw_write_epoch(),) + tuple((v._version, v.data_ptr()) for v in tensors)
-        if self._packed is not None and self._packed["ver"] == ver:
-            return self._packed
+        parameter changes or moves (`engine.weights_key`)."""
+        ver = engine.weights_key(list(self.parameters()) + list(self.buffers()))
+        p = self.__dict__.get("_syn_packed")
+        if p is not None and p["ver"] == ver:
+            return p
         sd = self.state_dict()
         dev = sd["decoder.model.0.weight"].device
         if dev.type != "cuda":
@@ -125,8 +121,8 @@ class RVQVAE(nn.Module):
         cbt = cb.transpose(1, 2).contiguous()
         cc = torch.sum(cbt ** 2, dim=1).contiguous()                        # quantizer.py:66: sum(k_w**2, dim=0)
         vm.codebooks, vm.codebooks_t, vm.code_sq = cb.data_ptr(), cbt.data_ptr(), cc.data_ptr()
-        self._packed = {"ver": ver, "model": vm, "keep": keep, "cb": cb, "cbt": cbt, "cc": cc, "ws": {}}
-        return self._packed
+        self._syn_packed = {"ver": ver, "model": vm, "keep": keep, "cb": cb, "cbt": cbt, "cc": cc, "ws": {}}
+        return self._syn_packed
 
     def _workspace(self, p, clips, t_pose, dev):
         key = (clips, t_pose)

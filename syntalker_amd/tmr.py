@@ -69,8 +69,9 @@ class _TmrStack(nn.Module):
         self.sequence_pos_encoding = PositionalEncoding(D, dropout)
         layer = nn.TransformerEncoderLayer(d_model=D, nhead=HEADS, dim_feedforward=FF, dropout=dropout, activation="gelu")
         self.seqTransEncoder = nn.TransformerEncoder(layer, num_layers=LAYERS, enable_nested_tensor=False)   # parameter container
-        self._packed = None
         super().train(False)
+
+    __getstate__ = engine.drop_caches         # (deepcopy / torch.save: without the packed copy - ctypes pointers into this module's tensors)
 
     def train(self, mode: bool = True):
         if mode:
@@ -83,11 +84,11 @@ class _TmrStack(nn.Module):
 
     def packed(self):
         """syn_tmr_model of this module: fragment-packed weights and views of the biases.  Rebuilt when a parameter changes (version
-        counters) or moves."""
-        tensors = self._stack_tensors()
-        ver = (engine.raw_write_epoch(),) + tuple((t._version, t.data_ptr()) for t in tensors)
-        if self._packed is not None and self._packed["ver"] == ver:
-            return self._packed
+        counters, `engine.weights_key`) or moves."""
+        ver = engine.weights_key(self._stack_tensors())
+        p = self.__dict__.get("_syn_packed")
+        if p is not None and p["ver"] == ver:
+            return p
         if not self.mu_token.is_cuda:
             raise _lib.SynHipError(f"{type(self).__name__} runs on the HIP kernels only: move the module to the GPU (no CPU fallback)")
         lib = _lib.load()
@@ -116,8 +117,8 @@ class _TmrStack(nn.Module):
             m.layer[i] = _lib.SynTmrLayer(pack(a.in_proj_weight), vec(a.in_proj_bias), pack(a.out_proj.weight), vec(a.out_proj.bias),
                                           vec(y.norm1.weight), vec(y.norm1.bias), pack(y.linear1.weight), vec(y.linear1.bias),
                                           pack(y.linear2.weight), vec(y.linear2.bias), vec(y.norm2.weight), vec(y.norm2.bias))
-        self._packed = {"ver": ver, "model": m, "keep": keep, "ws": {}}
-        return self._packed
+        self._syn_packed = {"ver": ver, "model": m, "keep": keep, "ws": {}}
+        return self._syn_packed
 
     def _encode(self, x: torch.Tensor, lengths):
         """x (B, L, nfeats) on the module's device, lengths None (all L) or a device int tensor (B,) -> (mu, logvar) fp32 (B, 256)."""

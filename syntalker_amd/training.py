@@ -56,16 +56,41 @@ def _pack_t(src: torch.Tensor, n: int, k: int) -> torch.Tensor:
     return out
 
 
-class WeightPacks:
-    """The bf16 fragment sets the step's Linear layers take - W for the forward GEMM, W^T for the data-gradient GEMM - packed from
-    the fp32 master weights in ONE launch per step (`syn_pack_weights`) instead of one launch per use: the weights only change in
-    optimizer.step().  `refresh()` at the top of every training forward; a weight is looked up by object identity and in-place version,
-    so a stale or foreign tensor simply takes the pack-on-the-spot path (`_packs_of`)."""
+class _PackRecords:
+    """Fragment sets of a model's weights, packed in ONE launch per step (a subclass's `refresh()`) instead of one launch per use: the weights only
+    change in optimizer.step().  A weight's record is found by its storage address - `ConvSplitFn` holds a 4-d view of the conv weight, which shares
+    the storage and the version counter - and keeps a weak reference (an address reused after the weight died is rejected) and the weight's in-place
+    version as of the last refresh (`engine.weights_key`).  A dead, moved or since-written weight misses, and the caller packs on the spot."""
 
-    def __init__(self, weights):
+    def __init__(self, owner=None):
+        self.owner = weakref.ref(owner) if owner is not None else (lambda: None)     # the model the cache belongs to (`_step_packs`)
+        self.items = {}                                          # address -> [weak reference, weights_key at the last refresh, packs]
+
+    def _add(self, w, packs):
+        self.items[w.data_ptr()] = [weakref.ref(w), None, packs]
+
+    def valid(self) -> bool:
+        return all(r() is not None and r().data_ptr() == ptr for ptr, (r, _, _) in self.items.items())
+
+    def _stamp(self):
+        for it in self.items.values():
+            it[1] = engine.weights_key([it[0]()])
+
+    def _packs(self, w):
+        it = self.items.get(w.data_ptr())
+        if it is None or it[0]() is None or it[0]().data_ptr() != w.data_ptr() or it[1] != engine.weights_key([w]):
+            return None
+        return it[2]
+
+
+class WeightPacks(_PackRecords):
+    """The bf16 fragment sets the step's Linear layers take - W for the forward GEMM, W^T for the data-gradient GEMM - packed from
+    the fp32 master weights by `syn_pack_weights`.  `refresh()` at the top of every training forward; a stale or foreign tensor takes
+    the pack-on-the-spot path (`_packs_of`)."""
+
+    def __init__(self, weights, owner=None):
         import numpy as np
-        self.owner = lambda: None                                # the model the cache belongs to (weak reference, set by its user)
-        self.items = {}
+        super().__init__(owner)
         jobs, self.max_frag = [], 0
         ok = []
         for w in weights:
@@ -86,14 +111,11 @@ class WeightPacks:
             jobs.append((w.data_ptr(), fwd.data_ptr(), N, Kp, 0, pad))       # fragments of W [N][Kp]
             jobs.append((w.data_ptr(), tr.data_ptr(), Kp, N, 1, pad))        # fragments of W^T [Kp][N] from the row-major [N][K]
             self.max_frag = max(self.max_frag, (N // 16) * (Kp // 32))
-            self.items[id(w)] = [weakref.ref(w), w.data_ptr(), -1, fwd, tr]
+            self._add(w, (fwd, tr))
         self.n_jobs = len(jobs)
         if jobs:
             arr = np.array(jobs, dtype=np.dtype([("src", "<u8"), ("out", "<u8"), ("n", "<i4"), ("k", "<i4"), ("t", "<i4"), ("src_dim", "<i4")]))
             self.jobs = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
-
-    def valid(self) -> bool:
-        return all(r() is not None and r().data_ptr() == ptr for r, ptr, *_ in self.items.values())
 
     def prefetch(self, transposed: bool):
         """One read pass over the forward / transposed fragment sets: whatever has been evicted from the memory-side cache since the
@@ -107,14 +129,10 @@ class WeightPacks:
             return
         _lib.check(_lib.load().syn_pack_weights(self.jobs.data_ptr(), self.n_jobs, self.max_frag, _lib.current_stream(self.jobs.device)),
                    "syn_pack_weights")
-        for it in self.items.values():
-            it[2] = it[0]()._version
+        self._stamp()
 
     def lookup(self, w):
-        it = self.items.get(id(w))
-        if it is None or it[0]() is not w or it[2] != w._version or it[1] != w.data_ptr():
-            return None, None
-        return it[3], it[4]
+        return self._packs(w) or (None, None)
 
 
 _packs: "WeightPacks | None" = None             # the step's packs of every Linear outside the blocks
@@ -584,7 +602,7 @@ def masked_smooth_l1(target, out, mask):
 def _rotary_tables(m, T, device):
     """(T, 32) tables cos / sin(position x inv_freq), fp32 like the reference's buffer (models/denoiser.py:324-343)."""
     inv = m.rel_pos.inv_freq
-    key = (inv.data_ptr(), inv._version, inv.device, T)
+    key = (engine.weights_key([inv]), inv.device, T)
     tab = m.__dict__.get("_syn_rotary_tables")
     if tab is None or tab[0] != key:
         with torch.no_grad():
@@ -720,49 +738,43 @@ class InputStageFn(torch.autograd.Function):
                 dwt, dbt, dwm, dbm, dwp, dbp, dw2, db2, dw3, db3)
 
 
-class ConvPacks:
+class ConvPacks(_PackRecords):
     """The hi / lo bf16 fragment sets of the audio encoder's Conv1d(k = 15) layers - the forward form of every layer and the
-    data-gradient form of every layer but the first of the chain - packed in ONE launch per training forward
-    (`syn_conv1d_pack_split_many`) instead of one launch per use (28 per step): the weights only change in optimizer.step().
-    `ConvSplitFn` looks a weight up by storage address and in-place version; a miss takes the per-call pack."""
+    data-gradient form of every layer but the first of the chain - packed by `syn_conv1d_pack_split_many` at the top of every training
+    forward (one launch instead of 28 per step); a miss takes the per-call pack (`_conv_pack_of`)."""
 
-    def __init__(self, convs):
+    def __init__(self, convs, owner=None):
         lib = _lib.load()
-        self.items, reqs, self.keep = {}, [], []
+        super().__init__(owner)
+        reqs = []
         for conv in convs:
             w = conv.weight
             cout, cin, stride = conv.out_channels, conv.in_channels, conv.stride[0]
             if not (w.is_cuda and w.dtype is torch.float32 and w.is_contiguous() and (cin, stride, cout) in ConvSplitFn.SUPPORTED):
                 continue
-            ent = {"ref": __import__("weakref").ref(w), "ptr": w.data_ptr(), "version": -1}
+            packs = []
             for transposed in (0, 1):
                 nb = lib.syn_conv1d_pack_bytes(cout, cin, stride, transposed)
                 hi, lo = torch.empty(nb, dtype=torch.uint8, device=w.device), torch.empty(nb, dtype=torch.uint8, device=w.device)
-                ent[transposed] = (hi, lo)
+                packs.append((hi, lo))
                 reqs.append((w.data_ptr(), hi.data_ptr(), lo.data_ptr(), cout, cin, stride, transposed))
-            self.items[w.data_ptr()] = ent
+            self._add(w, packs)
         self.lists = []
         for lo in range(0, len(reqs), _lib.SYN_CONV_PACK_MAX):
             chunk = reqs[lo:lo + _lib.SYN_CONV_PACK_MAX]
             arr = (_lib.SynConvPackReq * len(chunk))(*[_lib.SynConvPackReq(*r) for r in chunk])
             self.lists.append(arr)
-        self.device = next((e["ref"]().device for e in self.items.values()), None)
-
-    def valid(self) -> bool:
-        return all(e["ref"]() is not None and e["ref"]().data_ptr() == e["ptr"] for e in self.items.values())
+        self.device = next((r().device for r, _, _ in self.items.values()), None)
 
     def refresh(self):
         for arr in self.lists:
             _lib.check(_lib.load().syn_conv1d_pack_split_many(C.cast(arr, C.c_void_p), len(arr), _lib.current_stream(self.device)),
                        "syn_conv1d_pack_split_many")
-        for e in self.items.values():
-            e["version"] = e["ref"]()._version
+        self._stamp()
 
     def lookup(self, w, transposed):
-        e = self.items.get(w.data_ptr())
-        if e is None or e["ref"]() is None or e["version"] != w._version or e["ptr"] != e["ref"]().data_ptr():
-            return None
-        return e[int(bool(transposed))]
+        packs = self._packs(w)
+        return None if packs is None else packs[int(bool(transposed))]
 
 
 _conv_packs: "ConvPacks | None" = None
@@ -1085,7 +1097,7 @@ def _conv_raw(conv, x):
     raise _unsupported_conv("forward", cin, stride, pad, cout)
 
 
-_tracked: list = []
+_tracked: list = []             # the BatchNorms whose running statistics this training forward updates
 
 
 def _conv_bn_act(conv, bn, x, shortcut, act):
@@ -1100,8 +1112,8 @@ def _conv_bn_act(conv, bn, x, shortcut, act):
     else:
         z = BnActFn.apply(y, bn.weight, bn.bias, conv.bias, shortcut, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
     if bn.num_batches_tracked is not None:
-        _tracked.append(bn.num_batches_tracked)              # +1 as nn.BatchNorm1d.forward does in train() mode (checkpoints carry it):
-    return z                                                 # one launch for all of the encoder's counters, at the end of its forward
+        _tracked.append(bn)                                  # num_batches_tracked +1 as nn.BatchNorm1d.forward does in train() mode (checkpoints
+    return z                                                 # carry it): one launch for all of the encoder's counters, at the end of its forward
 
 
 def _conv_bn_eval(conv, bn, x):
@@ -1204,7 +1216,7 @@ def _wb_finalize(part, chunks, rows, bn, conv_bias, pair=None):
         jobs.append((pt, ch, c, b, None if cb is None else cb.detach(), stats, aff))
         outs.append((stats, aff))
         if b.num_batches_tracked is not None:
-            _tracked.append(b.num_batches_tracked)
+            _tracked.append(b)
     lib, st = _lib.load(), _lib.current_stream(dev)
     if pair is None:
         pt, ch, c, b, cb, stats, aff = jobs[0]
@@ -1499,14 +1511,12 @@ def _step_packs(m, training: bool):
     if pk is None or pk[0].owner() is not m or not (pk[0].valid() and pk[1].valid()):    # (a deep copy of the model brings the original's cache along)
         in_blocks = {id(mod.weight) for blk in m.mytimmblocks for mod in blk.modules() if isinstance(mod, nn.Linear)}
         lin_w = [mod.weight for mod in m.modules() if isinstance(mod, nn.Linear)]
-        pk = m.__dict__["_syn_weight_packs"] = (WeightPacks([w for w in lin_w if id(w) not in in_blocks]), WeightPacks([w for w in lin_w if id(w) in in_blocks]))
-        pk[0].owner = pk[1].owner = weakref.ref(m)
+        pk = m.__dict__["_syn_weight_packs"] = (WeightPacks([w for w in lin_w if id(w) not in in_blocks], m), WeightPacks([w for w in lin_w if id(w) in in_blocks], m))
     pk[0].refresh()
     _packs, _packs_blocks = pk
     cp = m.__dict__.get("_syn_conv_packs")
     if training and (cp is None or cp.owner() is not m or not cp.valid()):
-        cp = m.__dict__["_syn_conv_packs"] = ConvPacks([mod for mod in m.WavEncoder.modules() if isinstance(mod, nn.Conv1d)])
-        cp.owner = weakref.ref(m)
+        cp = m.__dict__["_syn_conv_packs"] = ConvPacks([mod for mod in m.WavEncoder.modules() if isinstance(mod, nn.Conv1d)], m)
     if training and cp.lists:
         cp.refresh()
         _conv_packs = cp
@@ -1526,8 +1536,6 @@ def train_forward(m, x, timesteps, y, drop_path: float = 0.1):
     if torch.is_grad_enabled() and any(getattr(p, "_syn_grad_handed", False) for p in m.parameters()):
         _reset_handed(m)                                       # a new step: every bound gradient buffer may be handed out again (`_grad_out`)
     _step_packs(m, training)
-    if training:
-        engine.note_raw_write()                                # (the BatchNorm running statistics are written by the finalize kernels, not by a tensor op)
     h3d = m.variant == "h3d"
     te = m.embed_timestep
     e = te.sequence_pos_encoder.pe[timesteps]                                   # (B,1,512)
@@ -1544,7 +1552,8 @@ def train_forward(m, x, timesteps, y, drop_path: float = 0.1):
     for blk in m.WavEncoder.feat_extractor:
         a = _wav_block(blk, a)
     if _tracked:
-        torch._foreach_add_(list(_tracked), 1)
+        torch._foreach_add_([bn.num_batches_tracked for bn in _tracked], 1)
+        torch.autograd.graph.increment_version([t for bn in _tracked for t in (bn.running_mean, bn.running_var)])   # (finalize kernels: `engine.weights_key`)
         _tracked.clear()
     # From here on rows are (clip, frame), not the reference's (frame, clip) (denoiser.py:151-176): every op below is row-wise or acts along the
     # frame axis of one clip, so the order is free - and this one needs no transposing copy between the encoder, the blocks and the output.

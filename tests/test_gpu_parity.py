@@ -784,6 +784,83 @@ def test_train_mode_step_runs_and_updates(beatx):
     assert torch.isfinite(out).all()
 
 
+@pytest.mark.parametrize("how", ["eager-step", "captured-step"])
+def test_frozen_modules_keep_their_packs_while_another_model_trains(how):
+    """The caches of derived weights key on the versions of their own module's tensors (`engine.weights_key`), and the raw-pointer writers of a training
+    step bump exactly what they write: training model A re-packs A and nothing else - not an EMA copy of A that samples between epochs (nor its captured
+    sampling loops), not a frozen RVQ-VAE, not the TMR motion encoder that computes the style vectors of every batch (scripts/train_from_config.py)."""
+    import copy
+    from syntalker_amd import rvqvae, tmr, training
+    from syntalker_amd.process import create_gaussian_diffusion
+    from syntalker_amd.resample import create_named_schedule_sampler
+    d = create_gaussian_diffusion()
+    a = _model("beatx").train()
+    ema = copy.deepcopy(a).eval()
+    rvq = rvqvae.build(78)
+    rvq.load_state_dict(synth.synth_vq_state_dict(78, seed=11))
+    rvq = rvq.to(DEV)
+    motion = tmr.ActorAgnosticEncoder(nfeats=623, vae=True, num_layers=4)
+    motion.load_state_dict(synth.synth_tmr_state_dict(motion))
+    motion = motion.to(DEV)
+    y = synth.to_device(synth.synth_clip_inputs(4, seed=81), DEV)
+    x0 = synth.synth_latent(4, seed=81, name="x0").to(DEV)
+    t = torch.tensor([100, 300, 500, 700], device=DEV)
+
+    def sample_ema():
+        with torch.no_grad():
+            d.p_sample_loop(ema, tuple(x0.shape), clip_denoised=False, model_kwargs={"y": y}, progress=False, skip_timesteps=997)
+
+    sample_ema()
+    opt = training.ClipAdam(a.parameters(), lr=1e-3, max_norm=0.99)
+    if how == "captured-step":
+        step = training.GraphedTrainStep(a, d, opt, x0, {"y": y})
+        run = lambda: step(x0, t, {"y": y})
+    else:
+        sampler = create_named_schedule_sampler("uniform", d)
+        run = lambda: training.train_step(a, d, sampler, opt, x0, {"y": y})
+    packs = (ema.packed(), rvq.packed(), motion.packed(), a.packed())
+    graphs = dict(ema._syn_graphs)
+    assert graphs
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    if how == "captured-step":
+        step.close()
+    assert ema.packed() is packs[0] and rvq.packed() is packs[1] and motion.packed() is packs[2]
+    assert a.packed() is not packs[3]                       # (that it holds the trained weights: test_sampling_after_training_sees_the_trained_weights)
+    sample_ema()
+    assert ema._syn_graphs == graphs                        # the same captured loops, none added
+
+
+def test_train_step_packs_every_weight_once(monkeypatch):
+    """The step's weights are packed once per step (`training.WeightPacks`, `training.ConvPacks`).  A lookup that misses is no error - the weight is then
+    packed on the spot, one launch per use - so it would only show as a slower step: two train-mode steps of the default model at 32 clips miss none."""
+    from syntalker_amd import training
+    from syntalker_amd.process import create_gaussian_diffusion
+    from syntalker_amd.resample import create_named_schedule_sampler
+    misses = []
+
+    def counted(lookup):
+        def wrapped(*args):
+            got = lookup(*args)
+            if got is None or got[0] is None:
+                misses.append(tuple(args[0].shape))
+            return got
+        return wrapped
+
+    monkeypatch.setattr(training, "_lookup_packs", counted(training._lookup_packs))
+    monkeypatch.setattr(training, "_lookup_conv_pack", counted(training._lookup_conv_pack))
+    d = create_gaussian_diffusion()
+    m = _model("beatx").train()
+    opt = training.ClipAdam(m.parameters(), lr=5e-5, betas=(0.5, 0.999), max_norm=0.99)
+    y = synth.to_device(synth.synth_clip_inputs(32, seed=83), DEV)
+    x0 = synth.synth_latent(32, seed=83, name="x0").to(DEV)
+    sampler = create_named_schedule_sampler("uniform", d)
+    for _ in range(2):
+        assert torch.isfinite(training.train_step(m, d, sampler, opt, x0, {"y": y}))
+    assert misses == []
+
+
 @pytest.mark.parametrize("variant", ["beatx", "h3d"])
 def test_used_model_deep_copies_and_pickles_like_an_nn_module(variant):
     """copy.deepcopy(model) (an EMA copy next to the trained model) and torch.save(model) / torch.load of a model that has already sampled and trained:
@@ -973,8 +1050,9 @@ def test_guided_small_batch_both_group_layouts(h3d):
 @pytest.mark.parametrize("how", ["captured-step", "eager-clipadam-eval-bn"])
 def test_sampling_after_training_sees_the_trained_weights(how):
     """The reference's trainer samples between epochs (diffusion_rvqvae_trainer.py: `val` / `test` from `train`).  The sampling kernels read folded, packed
-    copies of the weights (`MDM.packed()`), cached against the tensors' in-place version counters - which neither a hipGraph replay nor `ClipAdam`'s
-    raw-pointer update moves.  After training either way, the model's samples must equal those of a FRESH model loaded from its state_dict."""
+    copies of the weights (`MDM.packed()`), cached against the tensors' in-place version counters (`engine.weights_key`) - which a hipGraph replay and
+    `ClipAdam`'s raw-pointer update move by hand, for exactly the tensors they write.  After training either way, the model's samples must equal those of
+    a FRESH model loaded from its state_dict."""
     from syntalker_amd import training
     from syntalker_amd.process import create_gaussian_diffusion
     d = create_gaussian_diffusion()
@@ -1002,7 +1080,7 @@ def test_sampling_after_training_sees_the_trained_weights(how):
         step.close()
     else:
         m.eval()
-        m.differentiable_eval = True                       # fine-tuning with frozen BatchNorm statistics: nothing in the step touches a version counter
+        m.differentiable_eval = True                       # fine-tuning with frozen BatchNorm statistics: only ClipAdam.step moves the version counters
         for _ in range(3):
             opt.zero_grad(set_to_none=True)
             d.training_losses(m, x0, t, model_kwargs={"y": y})["loss"].mean().backward()

@@ -182,6 +182,23 @@ def test_packed_weights_follow_parameter_writes(motion):
     assert torch.equal(fresh.to(DEV).encode(x)[0], after)
 
 
+def test_used_encoder_deep_copies_and_pickles(motion):
+    """An encoder that has run holds a ctypes struct of raw pointers into its own packed tensors: copy.deepcopy and torch.save / torch.load take the
+    module without its `_syn_*` caches (`engine.drop_caches`), and each copy packs its own and encodes bit-equal to the original."""
+    import copy
+    import io
+    x = synth.synth_tmr_motion(3, 50).to(DEV)
+    mu, lv = motion.encode(x)
+    assert "_syn_packed" in motion.__dict__
+    buf = io.BytesIO()
+    torch.save(motion, buf)
+    buf.seek(0)
+    for m2 in (copy.deepcopy(motion), torch.load(buf, weights_only=False)):
+        assert not any(k.startswith("_syn_") for k in m2.__dict__)
+        mu2, lv2 = m2.encode(x)
+        assert torch.equal(mu2, mu) and torch.equal(lv2, lv)
+
+
 def _h3d_yaml(tmp_path, **extra):
     import json
     import yaml
