@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — denoising-steps/sec of the SynTalker hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--mode sample|train|guided]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--mode sample|train|guided] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K timed steps, --dump-outputs, the JSON
+line.  --full adds everything else this script measures (marked [--full] below): the CPU baseline, the other configurations, the
+small-batch probe, the steady state, the practical MFMA peak, the eager per-kernel split.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (one process per GPU,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); under an external launcher
@@ -18,16 +22,16 @@ Clips shard across GPUs with no collective (weak scaling: B per GPU is fixed).
 
 --mode train times BASELINE.json configs[2] instead (training step: 32 clips per GPU, uniform timestep sampler,
 training_losses forward + backward, clip 0.99, Adam 5e-5 / (0.5, 0.999), DDP all-reduce of the 29.6 M gradients over
-RCCL; reference seam train.py:87-94): metric = training samples/s over all GPUs + a forward / backward / optimiser split.
+RCCL; reference seam train.py:87-94): metric = training samples/s over all GPUs + a forward / backward / optimiser split [--full].
 
 --mode guided times BASELINE.json configs[3] and configs[4]: classifier-free guidance as ONE fused batch (cfg_sampler.py:10-167) over
 the h3d-style denoiser at the _hf.yaml shapes - `ClassifierFreeSampleModel` (scale 2.5, 2 reference evaluations per step, V = 2 variants,
-DDPM-1000 steps on the headline line and DDIM-50 steps beside it) and `TwoClassifierFreeSampleModel_Bodypart` (upper + lower prompts:
-9 reference evaluations, 4 unique variants, DDIM-50; h3d_diffusion_new_trainer.py:560-572): metric = guided clip-steps/s, plus
+DDPM-1000 steps on the headline line and DDIM-50 steps beside it [--full]) and `TwoClassifierFreeSampleModel_Bodypart` (upper + lower prompts:
+9 reference evaluations, 4 unique variants, DDIM-50; h3d_diffusion_new_trainer.py:560-572) [--full]: metric = guided clip-steps/s, plus
 reference-evaluation-equivalents/s and the roofline of the step kernel (algorithmic FLOPs = the V UNIQUE evaluations).
 
 The timed region is exactly what the contract says: W untimed steps, then K timed ones (`--prime N` adds N untimed 10-step replays in
-front of the warm-up, default 0; `steady_state` on the JSON line is a separate, later measurement of 200 more steps - a 1000-step
+front of the warm-up, default 0; `steady_state` on the --full line is a separate, later measurement of 200 more steps - a 1000-step
 loop spends 95 % of its time at clocks the device only reaches ~50 steps after a graph capture).
 
 --dump-outputs DIR writes what the timed path computed in its last timed step, as its caller would receive it, to DIR/<name>.npy
@@ -38,12 +42,13 @@ run with the same arguments repeats its inputs exactly and two builds compare ou
 Extra objects on the JSON line:
   roofline      dominant kernel: algorithmic FLOPs per launch / average launch duration (hipEvents on the replay
                 stream around every graph replay of the timed region, divided by the steps it holds; the step is one
-                kernel) vs the dense bf16 MFMA peak; one eager launch afterwards only names the kernel.
-  cpu_baseline  the as-written CPU restatement of the reference forward (oracle/) timed on the host cores.
-  train_step / train_step_ddp_1rank / guided   (default sample-mode line, one GPU; --no-extras skips them) BASELINE configs[2] - [4] through the same
+                kernel) vs the dense bf16 MFMA peak.  [--full] one eager step afterwards adds the per-stage split and the
+                launches per step (the five-kernel layer mode: the dominant kernel itself), and `practical_peak`.
+  cpu_baseline  [--full] the as-written CPU restatement of the reference forward (oracle/) timed on the host cores.
+  train_step / train_step_ddp_1rank / guided   [--full] (sample mode, one GPU; --no-extras skips them) BASELINE configs[2] - [4] through the same
                 code paths --mode train | guided time: the captured training step (20 timed steps), the same step under the DDP wrapper over a 1-rank
                 RCCL group (child process, 200 steps), CFG V = 2 with DDPM / DDIM-50 steps and the body-part wrapper V = 4 (20 timed steps each).
-  small_batch   step time at B = 1 .. 256 (the reference's own sampling scripts run B = 1).
+  small_batch   [--full] step time at B = 1 .. 256 (the reference's own sampling scripts run B = 1).
 """
 import argparse
 import ctypes as C
@@ -418,13 +423,13 @@ def run_train(args, rank, local, world, dev, dist):
             params = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()])
         dumped = dump_outputs(args.dump_outputs, {"loss": last["loss"].detach().reshape(1), "params": params}, rank, world)
     direct = training.direct_grad_report(model) if ddp else None   # gradients the backward wrote straight into the reducer's buckets
-    # forward / backward / clip+Adam split of one EAGER step (hipEvents on the current stream; rank 0 only reports it).  After a captured
-    # run the same three eager steps follow the timed region: issued from Python the step is host-bound, so these are upper bounds of the
-    # device time of each part (the rocprofv3 kernel-time split of the replayed step is profiles/r04_train_step_split.txt)
+    # [--full] forward / backward / clip+Adam split of one EAGER step (hipEvents on the current stream; rank 0 only reports it).  After a
+    # captured run the same three eager steps follow the timed region: issued from Python the step is host-bound, so these are upper bounds of
+    # the device time of each part (the rocprofv3 kernel-time split of the replayed step is profiles/r04_train_step_split.txt)
     split = None
     if graph:
         g.close()
-    if True:
+    if args.full:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         acc = [0.0, 0.0, 0.0]
         for _ in range(3):
@@ -456,7 +461,7 @@ def run_train(args, rank, local, world, dev, dist):
                        "parallelism": f"dp{world}: one process per GPU, DDP bucketed all-reduce of 29.6 M gradients over RCCL" if ddp else "single GPU",
                        "graph_replayed": graph, "ddp_wrapper": ddp, **({"graph_fallback": fallback} if fallback else {}),
                        **({"gradients_written_into_buckets": {"direct": direct[0], "bound": direct[1], "copied_by_the_reducer": direct[2][:24]}} if direct else {})},
-            "loss": round(loss, 5), "step_split": split,
+            "loss": round(loss, 5), **({"step_split": split} if split else {}),
             **({"dumped_outputs": {"dir": args.dump_outputs, "files": dumped, "what": "loss: the last timed step's loss; params: every parameter after "
                                                                                       "its update, concatenated in named_parameters() order"}} if dumped else {}),
             "roofline": {"bound": "mfma", "achieved": round(value / world * F_TRAIN / 1e12, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
@@ -547,26 +552,31 @@ def run_guided(args, rank, local, world, dev, dist):
     cfg = guidance.ClassifierFreeSampleModel(model)
     B3 = args.batch or 512
     main = one("configs[3] diffusion_rvqvae_128_hf.yaml shapes: ClassifierFreeSampleModel(scale 2.5) over the h3d-style denoiser, DDPM-1000 steps "
-               "(noise drawn in the epilogue), cond + uncond as one fused batch", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddpm, True, 2, True,
-               bool(args.dump_outputs))
-    d50 = one("configs[3], DDIM-50 steps (eta 0)", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddim, False, 2, False)
-    B4 = max(1, B3 // 2)
-    body = one("configs[4] diffusion_h3d.yaml: TwoClassifierFreeSampleModel_Bodypart (upper + lower prompts, audio scale 1, prompt scale 4), DDIM-50 steps",
-               guidance.TwoClassifierFreeSampleModel_Bodypart(model), B4, {"style_feature": parts}, coef_ddim, False, 9, False)
+               "(noise drawn in the epilogue), cond + uncond as one fused batch", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddpm, True, 2,
+               args.full, bool(args.dump_outputs))
+    more = {}
+    if args.full:                                               # the other two configurations
+        more["ddim50"] = one("configs[3], DDIM-50 steps (eta 0)", cfg, B3, {"scale": torch.ones(1, device=dev) * 2.5}, coef_ddim, False, 2, False)
+        B4 = max(1, B3 // 2)
+        more["bodypart_twocfg"] = one("configs[4] diffusion_h3d.yaml: TwoClassifierFreeSampleModel_Bodypart (upper + lower prompts, audio scale 1, "
+                                      "prompt scale 4), DDIM-50 steps", guidance.TwoClassifierFreeSampleModel_Bodypart(model), B4, {"style_feature": parts},
+                                      coef_ddim, False, 9, False)
     if rank != 0:
         return None
+    if args.full:                                               # (measured on rank 0 only)
+        more["steady_state_ms_per_step"] = main.get("steady_state_ms_per_step")
     return {"metric": "guided denoising-steps/sec (128-frame clips, classifier-free guidance as one fused batch)", "value": main["guided_clip_steps_per_s"],
             "unit": "guided clip-steps/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": main["ms_per_step"], "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": main["workload"], "clips_per_gpu": B3, "variants": main["variants"], "global_clips": world * B3,
                        "parallelism": f"clip-sharded x{world}, no collective", "primed_steps": args.prime * LOOP_CH},
             "reference_evaluation_equivalents_per_s": main["reference_evaluation_equivalents_per_s"],
-            "roofline": main["roofline"], "steady_state_ms_per_step": main.get("steady_state_ms_per_step"), "per_clip_conditioning": main.get("per_clip_conditioning"),
-            **({"dumped_outputs": main["dumped_outputs"]} if "dumped_outputs" in main else {}), "ddim50": d50, "bodypart_twocfg": body}
+            "roofline": main["roofline"], "per_clip_conditioning": main.get("per_clip_conditioning"),
+            **({"dumped_outputs": main["dumped_outputs"]} if "dumped_outputs" in main else {}), **more}
 
 
 def extras(args, local, dev) -> dict:
-    """BASELINE configs[2] - [4] on the default 1-GPU line: `train_step` (the captured training step of --mode train, 20 timed steps; plus
+    """BASELINE configs[2] - [4] on the --full 1-GPU sample line: `train_step` (the captured training step of --mode train, 20 timed steps; plus
     the SAME step under the DDP wrapper over a 1-rank RCCL group, run as a child process so that a collective that aborts cannot take
     the line with it) and `guided` (--mode guided's three workloads, 20 timed steps each).  Same code paths as the modes themselves."""
     import subprocess
@@ -629,9 +639,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default 1024 in sample mode, 32 in train mode)")
     ap.add_argument("--m-tile", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: CPU baseline, the other configurations, small-batch probe, "
+                         "steady state, practical MFMA peak, eager per-kernel split (a plain run times the headline workload only)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-small-batch", action="store_true", help="skip the B = 1 / 8 / 32 probe (clean per-kernel profiles)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-small-batch", action="store_true", help="--full without the B = 1 .. 256 probe (clean per-kernel profiles)")
     ap.add_argument("--mode", choices=("sample", "train", "guided"), default="sample",
                     help="sample: BASELINE configs[1] (DDPM p_sample_loop steps); train: configs[2] (DDP training step, 32 clips/GPU); "
                          "guided: configs[3] / [4] (classifier-free guidance as one fused batch, h3d-style denoiser)")
@@ -646,7 +659,7 @@ def main():
                     help="map the ranks onto the GPUs that exist (rank % count) - with --backend gloo a functional check of the N > 1 path on a 1-GPU box; "
                          "its throughput is NOT a scaling measurement")
     ap.add_argument("--no-extras", action="store_true",
-                    help="sample mode: skip the train_step / guided sub-objects (BASELINE configs[2]-[4]) the default 1-GPU line carries")
+                    help="--full sample mode: skip the train_step / guided sub-objects (BASELINE configs[2]-[4]) and the practical peak")
     ap.add_argument("--torch-adam", action="store_true", help="train mode: torch.nn.utils.clip_grad_norm_ + torch.optim.Adam(fused) instead of training.ClipAdam (A/B)")
     ap.add_argument("--inject-capture-failure", action="store_true", help="train mode, test hook: the step's hipGraph capture raises, the run falls back to the eager step")
     ap.add_argument("--dry-run", action="store_true",
@@ -703,7 +716,7 @@ def main():
         out = run_guided(args, rank, local, world, dev, dist)
     else:
         out = run_sample(args, rank, local, world, dev, dist)
-    if rank == 0 and world == 1 and args.mode == "sample" and not args.dry_run and not args.no_extras:
+    if rank == 0 and world == 1 and args.mode == "sample" and not args.dry_run and args.full and not args.no_extras:
         out.update(extras(args, local, dev))
     if rank == 0:
         out["rccl_ranks" if not (args.dry_run or args.backend == "gloo") else "gloo_ranks"] = ranks_seen
@@ -833,20 +846,20 @@ def run_sample(args, rank, local, world, dev, dist):
     coef = engine.posterior_coefs(diff.tables(), dev)
     sb.set_rng(1234, first_clip=rank * B)
     kept = {} if args.dump_outputs else None
-    dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, True, K, W, args.prime, world, dist, dev, rank == 0, kept)
+    dt, replay_ms, launch_ms, steady_ms = timed_loop(pm, sb, coef, True, K, W, args.prime, world, dist, dev, rank == 0 and args.full, kept)
     dumped = dump_outputs(args.dump_outputs, kept, rank, world) if kept is not None else None
     CH = LOOP_CH
 
     if rank == 0:
         value = world * B * K / dt
-        # ---- per-kernel durations: hipEvents around every launch of 5 eager steps ----------------
+        # ---- [--full] per-kernel durations: hipEvents around every launch of 5 eager steps ----------------
         ms = (C.c_float * 8)()
         cnt = (C.c_int32 * 8)()
         tot, launches = [0.0] * 8, [0] * 8
         reps = 5 if args.layer_mode == 1 else 1     # single-kernel steps are timed by the replay brackets; one eager launch
-                                                         # only names the kernel (keeps the rocprofv3 average = the replay average)
+                                                         # only counts the kernel's launches (keeps the rocprofv3 average = the replay average)
         frag = bool(getattr(sb, "fragment", False))   # the step runs on the wave-per-sequence kernel (latent in fragment order):
-        if frag:                                      # every k_seq launch of this command is one CH-step replay (no eager launch
+        if frag or not args.full:                     # every k_seq launch of this command is one CH-step replay (no eager launch
             reps = 0                                  # here: the rocprofv3 average of the kernel stays the replay average)
         for r in range(reps):
             sb.t_coef.fill_(500); sb.t_model.fill_(500)
@@ -877,13 +890,19 @@ def run_sample(args, rank, local, world, dev, dist):
                 slices = 1                                    # (a single step is one launch whatever the batch)
             d = {"ms": 0.0, "launches": slices, "flops": F_STEP * B * spl}
             avg_s = (launch_ms if spl == CH else replay_ms) * 1e-3 / slices
-        else:
+        elif reps:
             dom = max(by_kernel, key=lambda k: by_kernel[k]["ms"])
             d = by_kernel[dom]
             avg_s = d["ms"] * 1e-3 / d["launches"]
             if args.layer_mode in (0, 3, 4, 5):      # the step IS one kernel: use the hipEvent brackets of the K timed replays
                 avg_s = replay_ms * 1e-3
-        achieved = d["flops"] / d["launches"] / avg_s
+        elif args.layer_mode != 1:                   # no eager step: the one kernel of the step and its FLOPs, its launches per step uncounted
+            dom, fl = STAGE_INFO["fc2_gemm"]
+            d = {"ms": 0.0, "launches": None, "flops": fl * B}
+            avg_s = replay_ms * 1e-3
+        else:                                        # five kernels per block: no dominant kernel without the eager steps
+            dom = d = None
+        achieved = d["flops"] / (d["launches"] or 1) / avg_s if d else None
         # HBM/fabric bytes per launch come from separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this
         # same command, summarised and committed under profiles/; null when no summary matches this batch size.
         traffic = None
@@ -898,15 +917,18 @@ def run_sample(args, rank, local, world, dev, dist):
         if traffic is not None and traffic / avg_s > 8.0e12:       # more bytes than HBM can move in one launch: a parsing artefact
             print(f"bench.py: roofline.traffic {traffic} B / {avg_s * 1e6:.0f} us exceeds 8 TB/s - dropped", file=sys.stderr)
             traffic = None
-        roofline = {"bound": "mfma", "kernel": dom.replace("MT", str(args.m_tile or "auto")),
-                    "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
-                    "frac": round(achieved / PEAK_BF16, 4), "traffic": traffic,
-                    "avg_launch_us": round(avg_s * 1e6, 2), "launches_per_step": d["launches"] / spl, "steps_per_launch": spl,
-                    "whole_step_frac": round(value / world * F_STEP / PEAK_BF16, 4),
-                    "timed_region_replay_ms": round(replay_ms, 4),
-                    "timed_region_replays_ms_per_step": getattr(timed_loop, "last_replays_ms", None),
-                    "eager_stage_ms_per_step": {rename.get(k, k): round(v, 4) for k, v in stage_ms.items()}}
-        if world == 1 and not args.no_extras:
+        roofline = {"bound": "mfma"}
+        if d:
+            roofline.update({"kernel": dom.replace("MT", str(args.m_tile or "auto")),
+                             "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_BF16, 4), "traffic": traffic,
+                             "avg_launch_us": round(avg_s * 1e6, 2), "launches_per_step": d["launches"] and d["launches"] / spl, "steps_per_launch": spl})
+        roofline.update({"whole_step_frac": round(value / world * F_STEP / PEAK_BF16, 4),
+                         "timed_region_replay_ms": round(replay_ms, 4),
+                         "timed_region_replays_ms_per_step": getattr(timed_loop, "last_replays_ms", None)})
+        if args.full:
+            roofline["eager_stage_ms_per_step"] = {rename.get(k, k): round(v, 4) for k, v in stage_ms.items()}
+        if world == 1 and args.full and not args.no_extras:
             try:
                 pp = practical_peak(dev)
                 roofline["practical_peak"] = pp
@@ -926,15 +948,16 @@ def run_sample(args, rank, local, world, dev, dist):
                             f"once per clip, outside the timed region): {cond_ms_per_clip:.3f} ms/clip = "
                             f"{cond_ms_per_clip / (dt / K * 1e3 / B):.0f} denoising steps' worth",
             "roofline": roofline,
-            "steady_state": {"ms_per_step": round(steady_ms, 4), "clip_steps_per_s": round(B / steady_ms * 1e3, 1),
-                             "whole_step_frac": round(B / steady_ms * 1e3 * F_STEP / PEAK_BF16, 4),
-                             "note": "200 further steps after the timed region (wall clock, this rank): the clocks a 1000-step loop runs at"},
         }
+        if steady_ms is not None:
+            out["steady_state"] = {"ms_per_step": round(steady_ms, 4), "clip_steps_per_s": round(B / steady_ms * 1e3, 1),
+                                   "whole_step_frac": round(B / steady_ms * 1e3 * F_STEP / PEAK_BF16, 4),
+                                   "note": "200 further steps after the timed region (wall clock, this rank): the clocks a 1000-step loop runs at"}
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped, "what": "x: the latent after the last timed step, as p_sample_loop returns it"}
-        if args.layer_mode == 0 and not args.no_small_batch and world == 1:
+        if args.full and args.layer_mode == 0 and not args.no_small_batch and world == 1:
             out["small_batch"] = small_batch_probe(pm, coef, dev)
-        if not args.no_cpu and world == 1:      # the CPU baseline is a 1-GPU-run item: the other ranks would only wait for it
+        if args.full and not args.no_cpu and world == 1:      # the CPU baseline is a 1-GPU-run item: the other ranks would only wait for it
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
         return out

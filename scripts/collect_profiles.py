@@ -23,8 +23,8 @@ def val(part, kernel, col):
         if kernel in r["kernel"]:
             return float(r[col])
     raise KeyError((part, kernel, col))
-notes = {"b1024": "bench.py --steps 100 --warmup 10 --no-small-batch, B = 1024 clips: wave-per-sequence whole-step kernel k_seq, every launch = one persistent 10-step replay (syn_denoise_steps)",
-         "b8": "bench.py --batch 8 --steps 300 --warmup 20 --no-small-batch: persistent small-batch kernel k_lat, one clip per XCD"}
+notes = {"b1024": "bench.py --full --steps 100 --warmup 10 --no-small-batch, B = 1024 clips: wave-per-sequence whole-step kernel k_seq, every launch = one persistent 10-step replay (syn_denoise_steps)",
+         "b8": "bench.py --full --batch 8 --steps 300 --warmup 20 --no-small-batch: persistent small-batch kernel k_lat, one clip per XCD"}
 for b, note in notes.items():
     subprocess.run([sys.executable, os.path.join(R, "scripts/summarize_stats.py"), os.path.join(R, f"gpurun_out/prof_final_{b}/kernel_stats.csv"),
                     os.path.join(R, f"profiles/{tag}_final_kernel_stats_{b}.txt"), f"{tag} final: {note}"], check=True)

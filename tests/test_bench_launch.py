@@ -176,3 +176,31 @@ def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
         assert out["dumped_outputs"]["files"]["x"] == {"shape": [64, 1536, 1, 32], "rows": "all"}
         got.append(np.load(d / "x.npy"))
     assert got[0].dtype == np.float32 and np.isfinite(got[0]).all() and np.array_equal(got[0], got[1])
+
+
+@pytest.mark.gpu
+def test_plain_run_carries_the_headline_and_full_run_the_rest():
+    """A plain run times the headline workload and nothing else: no CPU baseline, other configuration, probe or second measurement on its line.
+    `--full` adds them (here without the train / guided sub-objects and the practical peak: --no-extras)."""
+    def line(*extra):
+        e = dict(os.environ); e.pop("WORLD_SIZE", None)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--batch", "64", *extra],
+                           capture_output=True, text=True, timeout=600, env=e)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain = line()
+    assert plain["metric"] == "denoising-steps/sec (128-frame clips)" and plain["unit"] == "clip-steps/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "bf16" and plain["steps"] == 12 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert not {"cpu_baseline", "small_batch", "steady_state", "train_step", "train_step_ddp_1rank", "guided"} & set(plain)
+    assert "eager_stage_ms_per_step" not in plain["roofline"] and "practical_peak" not in plain["roofline"]
+    assert plain["roofline"]["kernel"] and plain["roofline"]["frac"] > 0 and len(plain["roofline"]["timed_region_replays_ms_per_step"]) == 3
+    full = line("--full", "--no-extras", "--cpu-seconds", "0.3")
+    assert full["cpu_baseline"]["value"] > 0 and full["small_batch"]["us_per_step"] and full["steady_state"]["ms_per_step"] > 0
+    assert full["roofline"]["eager_stage_ms_per_step"] and full["roofline"]["launches_per_step"] >= 1
+    assert full["roofline"]["kernel"] == plain["roofline"]["kernel"]
+
+
+def test_bench_dry_run_takes_full():
+    r, lines = _run("--full")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(lines[0])["dry_run"] is True
