@@ -647,6 +647,49 @@ int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* s
 int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
                    float* mu, float* logvar, void* stream);
 
+/* ---- FGD motion embedder (models/motion_representation.py:67-75 VAESKConv.map2latent = LocalEncoder, models/motion_encoder.py:698-787;
+ * diffusion_rvqvae_trainer.py:613-619, 716-718) ----------------------------------------------------------------------------------------------
+ * Four SkeletonResidual layers (models/utils/skeleton.py:547-586) over the SMPL-X edge graph, frames halved by each:
+ *     r = GroupNorm(10, cout)(conv1d(x, W*M, b, kernel 4, stride 2, zero pad 1)),  s = conv1d(x, Ws*Ms, bs, kernel 1, stride 2),
+ *     out = tanh(P (r + s))                  (P: SkeletonPool's mean pooling, :162-235; identity where the layer keeps its edges)
+ * GroupNorm per clip over cout / 10 channels x all frames, eps 1e-5.  fp32 operands on v_mfma_f32_16x16x4_f32 (exact fp32 products). */
+#define SYN_SKEL_LAYERS   4
+#define SYN_SKEL_MAX_C    384      /* input / output channels of a layer (its 34-frame input window is staged in LDS, 64 KB at most) */
+#define SYN_SKEL_POOL_MAX 4        /* inputs one pooled channel averages */
+#define SYN_SKEL_MAX_CLIPS 65536  /* and at most 2^24 clip x 16-frame tiles in layer 0 */
+
+typedef struct syn_skel_layer {
+    const float*   w;          /* syn_skel_pack_weight's fragments: 64 floats per kept chunk                                        */
+    const int32_t* chunk_off;  /* [2 roundup(cout, 16) / 16 + 1]: kept chunks of output-column tile t are chunk_off[t] .. chunk_off[t+1] - 1 */
+    const int32_t* chunk_k;    /* per kept chunk: (tap << 16) | first input channel (a multiple of 4) of its 4 consecutive channels    */
+    const float*   bias;       /* [2 roundup(cout, 16)]: residual.0.bias | shortcut.bias, each zero-padded to roundup(cout, 16)          */
+    const float*   gn_g;       /* residual.1.weight [cout] */
+    const float*   gn_b;       /* residual.1.bias   [cout] */
+    const int32_t* pool_src;   /* [out_width][SYN_SKEL_POOL_MAX]: channels of (r + s) an output channel averages, -1 = none          */
+    const float*   pool_w;     /* [out_width][SYN_SKEL_POOL_MAX]: their weights (common.0.weight's nonzeros; 1 for identity)        */
+    int32_t        cin;        /* input channels (the previous layer's out_width)                                                  */
+    int32_t        cout;       /* conv output channels, a multiple of 10                                                           */
+    int32_t        out_width;  /* channels after the pooling                                                                       */
+    int32_t        reserved;
+} syn_skel_layer;
+
+typedef struct syn_skel_model {
+    syn_skel_layer layer[SYN_SKEL_LAYERS];
+} syn_skel_model;
+
+/* One layer's weights, both branches in one matrix: column n < cout_p = roundup(cout, 16) is residual.0's output channel n, column
+ * cout_p + n the shortcut's; row k = tap * roundup(cin, 4) + c (the shortcut reads tap 1, x[2t], only).  w [cout][cin][4] * mask,
+ * ws [cout][cin][1] * ms, gathered for the kept chunks listed in chunk_off / chunk_k (the caller chooses them: chunks holding a nonzero)
+ * into out [chunk_off[last]][64] as the MFMA's B operand (lane l: row 4 chunk + (l >> 4), column 16 t + (l & 15)).  Once per weight change. */
+int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, const float* ms, int32_t cout, int32_t cin, const int32_t* chunk_off,
+                         const int32_t* chunk_k, float* out, void* stream);
+/* x fp32 [n_clips][n_frames][layer[0].cin] -> out fp32 [n_clips][n_frames / 16][layer[3].out_width].  n_frames a positive multiple of 16,
+ * 1 <= n_clips <= SYN_SKEL_MAX_CLIPS.  workspace: per layer i (T = n_frames >> (i + 1)), the pre-norm r | s fp32 [n_clips][T][2 roundup(cout, 16)]
+ * then the GroupNorm partial sums fp64 [n_clips][ceil(T / 16)][10][sum, sum of squares], each region rounded up to 256 bytes.  Five launches
+ * (a conv per layer, each normalising its input while staging it; one for the last layer's output), no allocation, no sync, no atomics:
+ * bitwise reproducible, and each clip independent of the others in the batch. */
+int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream);
+
 /* ResidualVQ.forward in eval mode (models/vq/residual_vq.py:91-140 over quantizer.py:62-69,143-171), fp32, 6 layers
  * of 512 codes x 512 dims: x [rows][512] -> q_f32 / q_bf16 [rows][512] (sum of the straight-through outputs), idx
  * [rows][6], sqerr [syn_vq_quantize_groups(rows)][6] (per-group sums of |residual - code|^2: commit loss numerators),

@@ -26,7 +26,7 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_bn_bwd_stats", "syn_train_stack_fwd", "syn_train_stack_bwd", "syn_train_stack_wgrad",
            "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
            "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
-           "syn_tmr_pack_weight", "syn_tmr_encode")
+           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_skel_pack_weight", "syn_skel_encode")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -136,6 +136,20 @@ class SynTmrLayer(C.Structure):
 class SynTmrModel(C.Structure):
     _fields_ = [("nfeats", i32), ("relu_in", i32), ("w_in", vp), ("b_in", vp), ("mu_token", vp), ("logvar_token", vp), ("pe", vp),
                 ("layer", SynTmrLayer * SYN_TMR_LAYERS)]
+
+
+SYN_SKEL_LAYERS = 4
+SYN_SKEL_MAX_C = 384        # include/syn_hip.h: channels of a layer
+SYN_SKEL_POOL_MAX = 4
+
+
+class SynSkelLayer(C.Structure):
+    _fields_ = [("w", vp), ("chunk_off", vp), ("chunk_k", vp), ("bias", vp), ("gn_g", vp), ("gn_b", vp), ("pool_src", vp), ("pool_w", vp),
+                ("cin", i32), ("cout", i32), ("out_width", i32), ("reserved", i32)]
+
+
+class SynSkelModel(C.Structure):
+    _fields_ = [("layer", SynSkelLayer * SYN_SKEL_LAYERS)]
 
 
 class SynHipError(RuntimeError):
@@ -264,6 +278,8 @@ def load():
     lib.syn_vq_forward_decoder.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, i32, vp, vp, vp]
     lib.syn_tmr_pack_weight.argtypes = [vp, i32, i32, vp, vp]
     lib.syn_tmr_encode.argtypes = [C.POINTER(SynTmrModel), vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.syn_skel_pack_weight.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.syn_skel_encode.argtypes = [C.POINTER(SynSkelModel), vp, i32, i32, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes"):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import yaml
 
-from . import checkpoint, rvqvae, synth
+from . import checkpoint, evaluator, rvqvae, synth
 from .process import create_gaussian_diffusion
 from .resample import create_named_schedule_sampler
 
@@ -102,6 +102,19 @@ def build_sampler(args, device="cuda", model_cls=None):
             _require(p, name)
             setattr(s, "trans_mean" if name.startswith("mean") else "trans_std", torch.from_numpy(np.load(p)).float().to(device))
     return s
+
+
+def build_evaluator(args, device="cuda", load: bool = True):
+    """The FGD evaluator as diffusion_rvqvae_trainer.py's `test()` uses it (`eval_copy`, configs/diffusion_rvqvae_128.yaml:8-10): VAESKConv
+    over the SMPL-X tree of `data_path_1`, loaded from `data_path + e_path` with the reference's loader.  A missing checkpoint raises;
+    load=False leaves the initialisation (the caller fills the weights)."""
+    m = evaluator.VAESKConv(args)
+    if load:
+        path = getattr(args, "data_path", "") + getattr(args, "e_path", "")
+        if not getattr(args, "e_path", None) or not os.path.isfile(path):
+            raise FileNotFoundError(f"the FGD evaluator's checkpoint data_path + e_path = {path!r} does not exist")
+        checkpoint.load_checkpoints(m, path)
+    return m.to(device)
 
 
 # what the reference's parser falls back to when the YAML omits the key (utils/config.py:204 `--grad_norm` default 0 = no clipping,

@@ -1686,6 +1686,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_rvq.inc"
 #include "syn_pose.inc"
 #include "syn_tmr.inc"
+#include "syn_skel.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2151,6 +2152,16 @@ int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* s
 int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
                    float* mu, float* logvar, void* stream) {
     return tmr::encode(m, features, n_seq, max_len, lengths, workspace, mu, logvar, stream);
+}
+
+// FGD motion embedder (syn_skel.inc)
+int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, const float* ms, int32_t cout, int32_t cin, const int32_t* chunk_off,
+                         const int32_t* chunk_k, float* out, void* stream) {
+    return skel::pack_weight(w, mask, ws, ms, cout, cin, chunk_off, chunk_k, out, stream);
+}
+
+int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
+    return skel::encode(m, x, n_clips, n_frames, workspace, out, stream);
 }
 
 int syn_test_gemm(const void* x_bf16, const void* w_packed, const float* bias, int32_t m_rows, int32_t n, int32_t k,

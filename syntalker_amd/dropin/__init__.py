@@ -29,9 +29,15 @@ _MAP = {
 _MAP_RVQ = {"models.vq.model": "syntalker_amd.dropin.models.vq.model"}
 
 
-def install(rvqvae: bool = False):
-    """Alias the hot-path modules under the reference's module names (rvqvae=True: also `models.vq.model.RVQVAE`)."""
-    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {})}.items():
+# opt-in for the same reason: the reference's models/motion_representation.py also holds the VAE / VQ-VAE classes its other trainers train;
+# this one carries the FGD evaluator (VAESKConv) only
+_MAP_EVAL = {"models.motion_representation": "syntalker_amd.dropin.models.motion_representation"}
+
+
+def install(rvqvae: bool = False, evaluator: bool = False):
+    """Alias the hot-path modules under the reference's module names (rvqvae=True: also `models.vq.model.RVQVAE`; evaluator=True: also
+    `models.motion_representation.VAESKConv`, the FGD evaluator)."""
+    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {}), **(_MAP_EVAL if evaluator else {})}.items():
         mod = importlib.import_module(ours)
         sys.modules[ref_name] = mod
         parent, _, leaf = ref_name.rpartition(".")

@@ -3,8 +3,9 @@
 The reference's FGD (dataloaders/data_tools.py:1615-1685, `FIDCalculator.frechet_distance` / `calculate_frechet_distance`)
 is the pytorch-fid formula  d^2 = |mu1 - mu2|^2 + Tr(C1 + C2 - 2 sqrt(C1 C2))  over embeddings of its `VAESKConv` motion
 encoder (weights/AESKConv_240_100.bin - not distributed with the repository).  This module is the formula, host side
-(numpy / scipy like the reference's), over whatever embedding the caller has: the evaluator's when its checkpoint is
-available, or `latent_embedding` - time-averaged sampler latents in a fixed seeded projection - as the stand-in.
+(numpy / scipy like the reference's), and `fgd`, which runs it over that encoder's embeddings (evaluator.VAESKConv on the HIP
+kernels) the way the reference's `test()` collects them.  `latent_embedding` - time-averaged sampler latents in a fixed seeded
+projection - is the stand-in where no evaluator is at hand.
 """
 from __future__ import annotations
 
@@ -42,3 +43,40 @@ def latent_embedding(latents, dim: int = 240, seed: int = 2021) -> np.ndarray:
     x = x.reshape(x.shape[0], -1, x.shape[-1]).mean(1)
     proj = np.random.RandomState(seed).randn(x.shape[-1], dim) / np.sqrt(x.shape[-1])
     return x @ proj
+
+
+def fgd(evaluator, rec_takes, tar_takes, vae_test_len: int = 32) -> float:
+    """The reference's FGD (diffusion_rvqvae_trainer.py:613-619, 716-718): every take trimmed to a multiple of `vae_test_len`, embedded
+    by `evaluator.map2latent` (a VAESKConv), its rows of `vae_length` collected over the takes, separately for the generated (`rec_takes`)
+    and ground-truth (`tar_takes`) poses, then `frechet_distance` of the two sets.
+
+    Takes are 6D poses of shape (n_i, 330) or (1, n_i, 330) - `_g_test`'s `rec_pose` / `tar_pose` - as tensors or arrays.  `test()` first
+    sends them through rotation matrices and back (:613-616); on `_g_test`'s output, which already went that way (:528-529), that is the
+    identity up to fp32 rounding, so it is not repeated here.  Takes of equal trimmed length share one batch (clips are independent in
+    the encoder); a take shorter than `vae_test_len` contributes no rows."""
+    import torch
+    dev = next(evaluator.parameters()).device
+    width = int(evaluator.vae_length)
+
+    def rows(takes):
+        trimmed = []
+        for t in takes:
+            t = torch.as_tensor(t).float()
+            if t.dim() == 3 and t.shape[0] == 1:
+                t = t[0]
+            if t.dim() != 2:
+                raise ValueError(f"fgd: a take must be (n, C) or (1, n, C), got {tuple(t.shape)}")
+            trimmed.append(t[: t.shape[0] - t.shape[0] % vae_test_len])
+        out = [None] * len(trimmed)
+        for n in sorted({t.shape[0] for t in trimmed}):
+            idx = [i for i, t in enumerate(trimmed) if t.shape[0] == n]
+            if n == 0:
+                for i in idx:
+                    out[i] = np.zeros((0, width))
+                continue
+            emb = evaluator.map2latent(torch.stack([trimmed[i] for i in idx]).to(dev)).reshape(len(idx), -1, width).cpu().numpy()
+            for k, i in enumerate(idx):
+                out[i] = emb[k]
+        return np.concatenate(out, 0) if out else np.zeros((0, width))
+
+    return frechet_distance(rows(rec_takes), rows(tar_takes))

@@ -239,3 +239,40 @@ def synth_tmr_text_model(path: str, seed: int = 33, layers: int = 2):
     model.save_pretrained(path)
     DistilBertTokenizer(os.path.join(path, "vocab.txt"), do_lower_case=True).save_pretrained(path)
     return path
+
+
+def synth_evaluator_state_dict(module: torch.nn.Module, seed: int = 41) -> dict:
+    """The seeded weights of a VAESKConv with the reference's keys: matrices N(0, 1/fan_in) over the WHOLE conv weight (values outside the
+    masks too, which only the masks keep out of the result), GroupNorm gains 1 + 0.1 N(0,1), biases 0.05 N(0,1); the neighbour masks and the
+    pooling matrices (`common.0.weight`) stay as the module builds them."""
+    sd = {}
+    for k, v in module.state_dict().items():
+        keep = k.endswith(".mask") or k.endswith("common.0.weight")
+        sd[k] = v.detach().clone() if keep else synth_tensor(k, v.shape, seed).to(v.dtype)
+    return sd
+
+
+def synth_evaluator_takes(lengths, seed: int, scale: float = 1.0, shift: float = 0.0) -> list:
+    """Takes of (n, 330) 6D-pose stand-ins (unit Gaussian, scaled and shifted), one per length."""
+    g = _gen("evaluator_takes", seed)
+    return [scale * torch.randn(n, 330, generator=g) + shift for n in lengths]
+
+
+def synth_evaluator_input(batch: int, frames: int, seed: int = 42) -> torch.Tensor:
+    """(B, frames, 330) input of the evaluator's golden cases."""
+    return torch.randn(batch, frames, 330, generator=_gen("evaluator_input", seed))
+
+
+EVALUATOR_CASES = ((2, 256, 42), (1, 1024, 43), (3, 16, 44))            # (B, n, seed) of tests/golden/evaluator_outputs.npz
+EVALUATOR_FGD_TAKES = {"tar": ((2000, 3300, 1500, 2600, 1000), 45, 1.0, 0.0), "rec": ((1800, 2900, 3100, 1333, 2400), 46, 0.9, 0.05)}
+
+
+def synth_smplx_model(data_path_1: str, parents) -> str:
+    """Write the one part of the SMPL-X model file the FGD evaluator reads - `kintree_table` - where VAESKConv looks for it under
+    `data_path_1`; returns the file's path."""
+    import os
+    import numpy as np
+    path = os.path.join(data_path_1, "smplx_models", "smplx", "SMPLX_NEUTRAL_2020.npz")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez(path, kintree_table=np.stack([np.asarray(parents, np.int64), np.arange(len(parents))]))
+    return path
