@@ -690,6 +690,69 @@ int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, con
  * bitwise reproducible, and each clip independent of the others in the batch. */
 int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream);
 
+/* ---- T2M text-motion co-embedding evaluator (utils/t2m_eval_tools.py:332-351 MovementConvEncoder, :564-639 TextEncoderBiGRUCo /
+ * MotionEncoderBiGRUCo; EvaluatorMDMWrapper :833-899), eval mode ---------------------------------------------------------------------------------
+ *   movement: Conv1d(619 -> 512, k4, s2, p1), LeakyReLU 0.2, Conv1d(512 -> 512, k4, s2, p1), LeakyReLU 0.2, Linear(512, 512)
+ *   motion:   Linear(512 -> 1024), bidirectional GRU H = 1024 over `lengths` steps from the learned initial state, forward | reverse final
+ *             state -> Linear(2048 -> 1024), LayerNorm, LeakyReLU 0.2, Linear(1024 -> 512)
+ *   text:     word_embs + Linear(15 -> 300)(pos_onehot), Linear(300 -> 512), bidirectional GRU H = 512, the same head (1024 -> 512 -> 512)
+ * GRU gates in torch's order r | z | n.  fp32 operands on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation) throughout. */
+#define SYN_T2M_POSE       619     /* pose channels the movement encoder reads (the first 619 of each `ld`-wide frame)   */
+#define SYN_T2M_MOVE       512
+#define SYN_T2M_MOTION_H   1024
+#define SYN_T2M_TEXT_H     512
+#define SYN_T2M_WORD       300
+#define SYN_T2M_POS        15
+#define SYN_T2M_EMB        512
+#define SYN_T2M_MAX_SEQ    65536
+#define SYN_T2M_MAX_FRAMES 1024    /* frames of a motion / tokens of a caption */
+#define SYN_T2M_MOTION     0       /* `kind` of syn_t2m_workspace_bytes */
+#define SYN_T2M_TEXT       1
+
+typedef struct syn_t2m_gru {       /* nn.GRU(H, H, bidirectional): H = 1024 (motion) or 512 (text)                              */
+    const float* w_ih;             /* packed (layout 0) [weight_ih_l0 ; weight_ih_l0_reverse], 6 H x H                          */
+    const float* b_ih;             /* [bias_ih_l0 ; bias_ih_l0_reverse], 6 H                                                     */
+    const float* w_hh[2];          /* packed (layout H) weight_hh_l0, weight_hh_l0_reverse, 3 H x H each                        */
+    const float* b_hh;             /* [bias_hh_l0 ; bias_hh_l0_reverse], 6 H                                                     */
+    const float* hidden;           /* the module's `hidden` (2, 1, H): initial state per direction                              */
+} syn_t2m_gru;
+
+typedef struct syn_t2m_head {      /* output_net: Linear(2 H -> H), LayerNorm(H), LeakyReLU, Linear(H -> 512); w1, w2 packed    */
+    const float* w1; const float* b1; const float* ln_g; const float* ln_b; const float* w2; const float* b2;
+} syn_t2m_head;
+
+typedef struct syn_t2m_model {     /* every w packed by syn_t2m_pack_weight (layout 0 unless noted), every bias plain fp32      */
+    const float* conv1_w; const float* conv1_b;            /* main.0 (512, 619, 4): packed with conv_cin 619                     */
+    const float* conv2_w; const float* conv2_b;            /* main.3 (512, 512, 4): packed with conv_cin 512                     */
+    const float* out_w;   const float* out_b;              /* out_net                                                             */
+    const float* motion_in_w; const float* motion_in_b;    /* MotionEncoderBiGRUCo.input_emb                                      */
+    syn_t2m_gru  motion_gru;  syn_t2m_head motion_head;
+    const float* pos_w;   const float* pos_b;              /* TextEncoderBiGRUCo.pos_emb (300, 15)                                */
+    const float* text_in_w; const float* text_in_b;        /* TextEncoderBiGRUCo.input_emb                                        */
+    syn_t2m_gru  text_gru;    syn_t2m_head text_head;
+} syn_t2m_model;                   /* an entry reads its own encoder's members only: a motion-only model may leave the text ones NULL */
+
+/* fp32 w [n][k] (nn.Linear; conv_cin 0) or [n][conv_cin][4] (nn.Conv1d k4, k = 4 conv_cin, packed with row tap * conv_cin + c) -> `out`,
+ * float4 MFMA fragments (element j of lane l: row 16 q + 4 (l >> 4) + j, column 16 tile + (l & 15); zero outside n x k).
+ * layout 0: the GEMM's order, roundup(n, 128) x roundup(k, 16) floats.  layout H (512 or 1024; n = 3 H, k = H): the recurrent kernel's
+ * consumption order (per wave of 8: H / 8 hidden units x 3 gates, K block by K block), 3 H x H floats.  Once per weight change. */
+int syn_t2m_pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, int32_t layout, float* out, void* stream);
+/* Bytes of `workspace` for a call (kind SYN_T2M_MOTION: max_len = n_frames; SYN_T2M_TEXT: max_len tokens); -1 for arguments the encoders
+ * refuse.  Dominated by W_ih x of every step, 6 H floats per sequence and step. */
+int64_t syn_t2m_workspace_bytes(int32_t n_seq, int32_t max_len, int32_t kind);
+/* motions fp32 [n_seq][n_frames][ld] (the first 619 channels of a frame are read; zero beyond a motion's own frames, as the loader pads
+ * them) -> out fp32 [n_seq][512], row i = sequence i.  lengths_dev: device int32 [n_seq] GRU steps per sequence (m_lens // 4, clamped to
+ * 0 .. T'', T' = (n_frames - 2) / 2 + 1, T'' = (T' - 2) / 2 + 1).  order_dev: device int32 [n_seq], a permutation: the recurrent kernel
+ * takes sequences order[16 b .. 16 b + 15] as workgroup b's tile and runs the tile for its longest member, so sort by length.
+ * 4 <= n_frames <= SYN_T2M_MAX_FRAMES, 1 <= n_seq <= SYN_T2M_MAX_SEQ.  8 launches, no allocation, no sync, no atomics, no inter-workgroup
+ * hand-off: bitwise reproducible, each sequence independent of the others in the batch. */
+int syn_t2m_encode_motion(const syn_t2m_model* m, const float* motions, int32_t n_seq, int32_t n_frames, int32_t ld, const int32_t* lengths_dev,
+                          const int32_t* order_dev, void* workspace, float* out, void* stream);
+/* word_embs fp32 [n_seq][max_len][300], pos_onehot fp32 [n_seq][max_len][15] -> out fp32 [n_seq][512]; lengths_dev: tokens per caption
+ * (clamped to 0 .. max_len), order_dev as above.  6 launches. */
+int syn_t2m_encode_text(const syn_t2m_model* m, const float* word_embs, const float* pos_onehot, int32_t n_seq, int32_t max_len,
+                        const int32_t* lengths_dev, const int32_t* order_dev, void* workspace, float* out, void* stream);
+
 /* ResidualVQ.forward in eval mode (models/vq/residual_vq.py:91-140 over quantizer.py:62-69,143-171), fp32, 6 layers
  * of 512 codes x 512 dims: x [rows][512] -> q_f32 / q_bf16 [rows][512] (sum of the straight-through outputs), idx
  * [rows][6], sqerr [syn_vq_quantize_groups(rows)][6] (per-group sums of |residual - code|^2: commit loss numerators),

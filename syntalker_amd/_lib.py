@@ -26,7 +26,8 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_bn_bwd_stats", "syn_train_stack_fwd", "syn_train_stack_bwd", "syn_train_stack_wgrad",
            "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
            "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
-           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_skel_pack_weight", "syn_skel_encode")
+           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_skel_pack_weight", "syn_skel_encode",
+           "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -150,6 +151,25 @@ class SynSkelLayer(C.Structure):
 
 class SynSkelModel(C.Structure):
     _fields_ = [("layer", SynSkelLayer * SYN_SKEL_LAYERS)]
+
+
+SYN_T2M_POSE, SYN_T2M_MOVE, SYN_T2M_MOTION_H, SYN_T2M_TEXT_H, SYN_T2M_WORD, SYN_T2M_POS, SYN_T2M_EMB = 619, 512, 1024, 512, 300, 15, 512
+SYN_T2M_MAX_SEQ, SYN_T2M_MAX_FRAMES = 65536, 1024       # include/syn_hip.h
+SYN_T2M_MOTION, SYN_T2M_TEXT = 0, 1
+
+
+class SynT2mGru(C.Structure):
+    _fields_ = [("w_ih", vp), ("b_ih", vp), ("w_hh", vp * 2), ("b_hh", vp), ("hidden", vp)]
+
+
+class SynT2mHead(C.Structure):
+    _fields_ = [("w1", vp), ("b1", vp), ("ln_g", vp), ("ln_b", vp), ("w2", vp), ("b2", vp)]
+
+
+class SynT2mModel(C.Structure):
+    _fields_ = [("conv1_w", vp), ("conv1_b", vp), ("conv2_w", vp), ("conv2_b", vp), ("out_w", vp), ("out_b", vp),
+                ("motion_in_w", vp), ("motion_in_b", vp), ("motion_gru", SynT2mGru), ("motion_head", SynT2mHead),
+                ("pos_w", vp), ("pos_b", vp), ("text_in_w", vp), ("text_in_b", vp), ("text_gru", SynT2mGru), ("text_head", SynT2mHead)]
 
 
 class SynHipError(RuntimeError):
@@ -280,13 +300,19 @@ def load():
     lib.syn_tmr_encode.argtypes = [C.POINTER(SynTmrModel), vp, i32, i32, vp, vp, vp, vp, vp]
     lib.syn_skel_pack_weight.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.syn_skel_encode.argtypes = [C.POINTER(SynSkelModel), vp, i32, i32, vp, vp, vp]
+    lib.syn_t2m_pack_weight.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.syn_t2m_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.syn_t2m_encode_motion.argtypes = [C.POINTER(SynT2mModel), vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.syn_t2m_encode_text.argtypes = [C.POINTER(SynT2mModel), vp, vp, i32, i32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes"):
+        if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes",
+                        "syn_t2m_workspace_bytes"):
             fn.restype = C.c_int
     lib.syn_wav_workspace_bytes.restype = C.c_int64
     lib.syn_conv1d_pack_bytes.restype = C.c_int64
     lib.syn_vq_workspace_bytes.restype = C.c_int64
+    lib.syn_t2m_workspace_bytes.restype = C.c_int64
     _lib = lib
     return lib
 

@@ -1687,6 +1687,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_pose.inc"
 #include "syn_tmr.inc"
 #include "syn_skel.inc"
+#include "syn_t2m.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2162,6 +2163,23 @@ int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, con
 
 int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
     return skel::encode(m, x, n_clips, n_frames, workspace, out, stream);
+}
+
+// T2M text-motion evaluator (syn_t2m.inc)
+int syn_t2m_pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, int32_t layout, float* out, void* stream) {
+    return t2m::pack_weight(w, n, k, conv_cin, layout, out, stream);
+}
+
+int64_t syn_t2m_workspace_bytes(int32_t n_seq, int32_t max_len, int32_t kind) { return t2m::workspace_bytes(n_seq, max_len, kind); }
+
+int syn_t2m_encode_motion(const syn_t2m_model* m, const float* motions, int32_t n_seq, int32_t n_frames, int32_t ld, const int32_t* lengths_dev,
+                          const int32_t* order_dev, void* workspace, float* out, void* stream) {
+    return t2m::encode_motion(m, motions, n_seq, n_frames, ld, lengths_dev, order_dev, workspace, out, stream);
+}
+
+int syn_t2m_encode_text(const syn_t2m_model* m, const float* word_embs, const float* pos_onehot, int32_t n_seq, int32_t max_len,
+                        const int32_t* lengths_dev, const int32_t* order_dev, void* workspace, float* out, void* stream) {
+    return t2m::encode_text(m, word_embs, pos_onehot, n_seq, max_len, lengths_dev, order_dev, workspace, out, stream);
 }
 
 int syn_test_gemm(const void* x_bf16, const void* w_packed, const float* bias, int32_t m_rows, int32_t n, int32_t k,

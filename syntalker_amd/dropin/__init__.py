@@ -34,10 +34,15 @@ _MAP_RVQ = {"models.vq.model": "syntalker_amd.dropin.models.vq.model"}
 _MAP_EVAL = {"models.motion_representation": "syntalker_amd.dropin.models.motion_representation"}
 
 
-def install(rvqvae: bool = False, evaluator: bool = False):
+# opt-in: the reference's `utils` package holds far more than the T2M evaluator (h3d_diffusion_new_trainer.py imports its logging and
+# rotation helpers from there); only `utils.t2m_eval_tools` - EvaluatorMDMWrapper and the evaluate_* metrics - is replaced
+_MAP_T2M = {"utils.t2m_eval_tools": "syntalker_amd.dropin.utils.t2m_eval_tools"}
+
+
+def install(rvqvae: bool = False, evaluator: bool = False, t2m: bool = False):
     """Alias the hot-path modules under the reference's module names (rvqvae=True: also `models.vq.model.RVQVAE`; evaluator=True: also
-    `models.motion_representation.VAESKConv`, the FGD evaluator)."""
-    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {}), **(_MAP_EVAL if evaluator else {})}.items():
+    `models.motion_representation.VAESKConv`, the FGD evaluator; t2m=True: also `utils.t2m_eval_tools`, the h3d text-motion evaluator)."""
+    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {}), **(_MAP_EVAL if evaluator else {}), **(_MAP_T2M if t2m else {})}.items():
         mod = importlib.import_module(ours)
         sys.modules[ref_name] = mod
         parent, _, leaf = ref_name.rpartition(".")

@@ -276,3 +276,50 @@ def synth_smplx_model(data_path_1: str, parents) -> str:
     os.makedirs(os.path.dirname(path), exist_ok=True)
     np.savez(path, kintree_table=np.stack([np.asarray(parents, np.int64), np.arange(len(parents))]))
     return path
+
+
+# ---- T2M text-motion evaluator (utils/t2m_eval_tools.py): weights of its three modules and loader-shaped batches ---------------------------
+T2M_FRAMES, T2M_TEXT_LEN, T2M_DIM_POSE = 196, 22, 623            # the h3d loader's padded shapes (max_motion_length, max_text_len + 2)
+T2M_STATE_SEEDS = {"movement_encoder": 51, "text_encoder": 52, "motion_encoder": 53}     # finest.tar's three dicts, tests/golden/t2m_evaluator_outputs.npz
+
+
+def synth_t2m_state_dict(module: torch.nn.Module, seed: int = 51) -> dict:
+    """Seeded weights of a MovementConvEncoder / MotionEncoderBiGRUCo / TextEncoderBiGRUCo at the scale the reference initialises them:
+    Xavier-normal Linear and Conv1d weights (its `init_weight`), GRU weights and biases uniform in +-1/sqrt(H) (torch's default), the other
+    biases 0.05 N(0,1) instead of its zeros, LayerNorm gains 1 + 0.1 N(0,1), `hidden` N(0,1); `module` supplies the keys and shapes."""
+    sd = {}
+    for k, v in module.state_dict().items():
+        g = _gen("t2m:" + k, seed)
+        shape = tuple(v.shape)
+        if k == "hidden":
+            t = torch.randn(shape, generator=g)
+        elif k.startswith("gru."):
+            bound = shape[-1] ** -0.5 if len(shape) == 2 else (shape[0] // 3) ** -0.5
+            t = (2 * torch.rand(shape, generator=g) - 1) * bound
+        elif len(shape) == 1:
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g) if k.endswith("output_net.1.weight") else 0.05 * torch.randn(shape, generator=g)
+        else:
+            field = 1
+            for s in shape[2:]:
+                field *= s
+            t = torch.randn(shape, generator=g) * (2.0 / ((shape[0] + shape[1]) * field)) ** 0.5
+        sd[k] = t.to(v.dtype)
+    return sd
+
+
+def synth_t2m_batch(n: int, seed: int, frames: int = T2M_FRAMES, text_len: int = T2M_TEXT_LEN, m_range=(40, T2M_FRAMES), cap_range=(4, T2M_TEXT_LEN),
+                    m_lens=None, cap_lens=None) -> tuple:
+    """One batch as the h3d evaluation loader collates it: (word_embs (n, text_len, 300), pos_onehot (n, text_len, 15), cap_lens (n) int64
+    descending, motions (n, frames, 623) zero beyond each motion's frames, m_lens (n) int64).  Lengths are drawn from the closed ranges unless
+    given; token slots beyond a caption hold values (the loader's padding tokens), which a packed sequence never reads."""
+    g = _gen("t2m_batch", seed)
+    if m_lens is None:
+        m_lens = torch.randint(m_range[0], min(m_range[1], frames) + 1, (n,), generator=g)
+    if cap_lens is None:
+        cap_lens = torch.randint(cap_range[0], min(cap_range[1], text_len) + 1, (n,), generator=g).sort(descending=True).values
+    m_lens, cap_lens = torch.as_tensor(m_lens, dtype=torch.int64), torch.as_tensor(cap_lens, dtype=torch.int64)
+    word = 0.4 * torch.randn(n, text_len, WORD_DIM, generator=g)
+    pos = torch.nn.functional.one_hot(torch.randint(0, 15, (n, text_len), generator=g), 15).float()
+    motions = torch.randn(n, frames, T2M_DIM_POSE, generator=g)
+    motions = motions * (torch.arange(frames)[None, :, None] < m_lens[:, None, None])
+    return word, pos, cap_lens, motions, m_lens
