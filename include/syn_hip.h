@@ -647,6 +647,43 @@ int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* s
 int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
                    float* mu, float* logvar, void* stream);
 
+/* ---- DistilBERT in front of the TMR text encoder (transformers' DistilBertModel as textencoder/distillbert_actor.py:44-49 calls it) ----
+ * token ids -> last_hidden_state: word_embeddings[id] + position_embeddings[position], LayerNorm; n_layers post-norm TransformerBlocks
+ * (q_lin | k_lin | v_lin as one 2304 x 768 product, 12 heads x 64 with scale 1/8 and keys >= length masked, out_lin + residual +
+ * sa_layer_norm, lin1 + erf GELU, lin2 + residual + output_layer_norm); every LayerNorm with eps 1e-12, dropout inactive.  GEMMs and both
+ * attention products on hi + lo bf16 operands (three MFMAs per product, fp32 accumulate), fp32 residual / LayerNorm / softmax. */
+#define SYN_BERT_D          768
+#define SYN_BERT_HEADS      12
+#define SYN_BERT_FF         3072
+#define SYN_BERT_MAX_LAYERS 12
+
+typedef struct syn_bert_layer {
+    const void*  w_qkv;  const float* b_qkv;      /* packed [q_lin; k_lin; v_lin].weight (2304 x 768), the three biases (2304)  */
+    const void*  w_out;  const float* b_out;      /* packed attention.out_lin (768 x 768), bias                                 */
+    const float* ln1_g;  const float* ln1_b;      /* sa_layer_norm                                                               */
+    const void*  w_fc1;  const float* b_fc1;      /* packed ffn.lin1 (3072 x 768), bias                                          */
+    const void*  w_fc2;  const float* b_fc2;      /* packed ffn.lin2 (768 x 3072), bias                                          */
+    const float* ln2_g;  const float* ln2_b;      /* output_layer_norm                                                           */
+} syn_bert_layer;
+
+typedef struct syn_bert_model {
+    int32_t      n_layers;                        /* 1 .. SYN_BERT_MAX_LAYERS                                                    */
+    int32_t      vocab;                           /* rows of `word`; ids are clamped to 0 .. vocab - 1 inside the kernel         */
+    int32_t      n_pos;                           /* rows of `pos` (>= max_len of a call)                                        */
+    int32_t      reserved;
+    const float* word;   const float* pos;        /* embeddings.word_embeddings (vocab x 768), position_embeddings (n_pos x 768), fp32, 16-byte aligned */
+    const float* emb_ln_g; const float* emb_ln_b; /* embeddings.LayerNorm                                                        */
+    syn_bert_layer layer[SYN_BERT_MAX_LAYERS];    /* packed with syn_tmr_pack_weight                                             */
+} syn_bert_model;
+
+/* ids int32 [n_seq][max_len] -> hidden fp32 [n_seq][max_len][768] (last_hidden_state); rows at or beyond a sequence's length are written as
+ * zeros.  lengths: device int32 [n_seq] valid tokens per sequence, a prefix (clamped to 0 .. max_len), NULL = all max_len.
+ * workspace: n_seq max_len x 24576 bytes (qkv fp32 2304, reused for a Linear's output before its LayerNorm | attention fp32 768 | FF hidden
+ * fp32 3072 per row), 16-byte aligned like `hidden`.  1 <= max_len <= SYN_TMR_MAX_LEN, 1 <= n_seq <= SYN_TMR_MAX_SEQ.
+ * 1 + 7 n_layers launches, no allocation, no sync. */
+int syn_bert_encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                    float* hidden, void* stream);
+
 /* ---- FGD motion embedder (models/motion_representation.py:67-75 VAESKConv.map2latent = LocalEncoder, models/motion_encoder.py:698-787;
  * diffusion_rvqvae_trainer.py:613-619, 716-718) ----------------------------------------------------------------------------------------------
  * Four SkeletonResidual layers (models/utils/skeleton.py:547-586) over the SMPL-X edge graph, frames halved by each:

@@ -26,7 +26,7 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_bn_bwd_stats", "syn_train_stack_fwd", "syn_train_stack_bwd", "syn_train_stack_wgrad",
            "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
            "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
-           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_skel_pack_weight", "syn_skel_encode",
+           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_bert_encode", "syn_skel_pack_weight", "syn_skel_encode",
            "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
@@ -137,6 +137,19 @@ class SynTmrLayer(C.Structure):
 class SynTmrModel(C.Structure):
     _fields_ = [("nfeats", i32), ("relu_in", i32), ("w_in", vp), ("b_in", vp), ("mu_token", vp), ("logvar_token", vp), ("pe", vp),
                 ("layer", SynTmrLayer * SYN_TMR_LAYERS)]
+
+
+SYN_TMR_MAX_SEQ = 65536
+SYN_BERT_D, SYN_BERT_HEADS, SYN_BERT_FF, SYN_BERT_MAX_LAYERS = 768, 12, 3072, 12      # include/syn_hip.h
+
+
+class SynBertLayer(C.Structure):
+    _fields_ = SynTmrLayer._fields_
+
+
+class SynBertModel(C.Structure):
+    _fields_ = [("n_layers", i32), ("vocab", i32), ("n_pos", i32), ("reserved", i32), ("word", vp), ("pos", vp), ("emb_ln_g", vp), ("emb_ln_b", vp),
+                ("layer", SynBertLayer * SYN_BERT_MAX_LAYERS)]
 
 
 SYN_SKEL_LAYERS = 4
@@ -298,6 +311,7 @@ def load():
     lib.syn_vq_forward_decoder.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, i32, vp, vp, vp]
     lib.syn_tmr_pack_weight.argtypes = [vp, i32, i32, vp, vp]
     lib.syn_tmr_encode.argtypes = [C.POINTER(SynTmrModel), vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.syn_bert_encode.argtypes = [C.POINTER(SynBertModel), vp, i32, i32, vp, vp, vp, vp]
     lib.syn_skel_pack_weight.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.syn_skel_encode.argtypes = [C.POINTER(SynSkelModel), vp, i32, i32, vp, vp, vp]
     lib.syn_t2m_pack_weight.argtypes = [vp, i32, i32, i32, i32, vp, vp]

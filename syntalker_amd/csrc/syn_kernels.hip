@@ -1686,6 +1686,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_rvq.inc"
 #include "syn_pose.inc"
 #include "syn_tmr.inc"
+#include "syn_bert.inc"
 #include "syn_skel.inc"
 #include "syn_t2m.inc"
 
@@ -2153,6 +2154,12 @@ int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* s
 int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
                    float* mu, float* logvar, void* stream) {
     return tmr::encode(m, features, n_seq, max_len, lengths, workspace, mu, logvar, stream);
+}
+
+// DistilBERT in front of the TMR text encoder (syn_bert.inc)
+int syn_bert_encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                    float* hidden, void* stream) {
+    return bert::encode(m, ids, n_seq, max_len, lengths, workspace, hidden, stream);
 }
 
 // FGD motion embedder (syn_skel.inc)

@@ -241,6 +241,22 @@ def synth_tmr_text_model(path: str, seed: int = 33, layers: int = 2):
     return path
 
 
+TMR_RAGGED_TOKENS = (2, 16, 17, 64, 65, 254)      # token counts each side of a 16-row MFMA tile and of a 64-query tile, the empty prompt, the maximum
+
+
+def synth_tmr_prompts(token_lengths, seed: int = 35) -> list:
+    """Prompts of exactly `token_lengths` tokens each ([CLS] + words + [SEP]; every word of the synthetic vocabulary is one token, 2 tokens is
+    the empty prompt), the words a seeded draw from the synthetic word list."""
+    words = sorted(set(_TMR_WORDS))
+    g = _gen("tmr_prompts", seed)
+    out = []
+    for n in token_lengths:
+        if n < 2:
+            raise ValueError("a tokenized prompt has at least [CLS] and [SEP]")
+        out.append(" ".join(words[i] for i in torch.randint(0, len(words), (n - 2,), generator=g).tolist()))
+    return out
+
+
 def synth_evaluator_state_dict(module: torch.nn.Module, seed: int = 41) -> dict:
     """The seeded weights of a VAESKConv with the reference's keys: matrices N(0, 1/fan_in) over the WHOLE conv weight (values outside the
     masks too, which only the masks keep out of the result), GroupNorm gains 1 + 0.1 N(0,1), biases 0.05 N(0,1); the neighbour masks and the
