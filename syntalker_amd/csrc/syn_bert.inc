@@ -11,6 +11,8 @@ using tmr::kArow;
 using tmr::kBM;
 using tmr::kBN;
 using tmr::kKC;
+using tmr::launched;
+using tmr::load8;
 using tmr::split8;
 
 constexpr int kD = SYN_BERT_D, kQKV = 3 * SYN_BERT_D, kFF = SYN_BERT_FF, kHeads = SYN_BERT_HEADS, kHd = 64;
@@ -28,11 +30,6 @@ struct GemmArgs {
 __device__ __forceinline__ bool row_valid(const int32_t* lengths, int L, int M, int i) {
     if (i >= M) return false;
     return lengths ? i % L < lengths[i / L] : true;
-}
-
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
 // 256 threads; wave w owns output columns [64 w, 64 w + 64) of the tile, all 64 rows: acc[m tile][n tile] (k_tmr_gemm's main loop).
@@ -309,8 +306,7 @@ template <int EPI>
 int gemm(const GemmArgs& a, int n_cols, hipStream_t st) {
     dim3 grid((unsigned)((a.M + kBM - 1) / kBM), (unsigned)(n_cols / kBN));
     hipLaunchKernelGGL(k_bert_gemm<EPI>, grid, dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_bert_gemm launch", e);
+    return launched("k_bert_gemm launch");
 }
 
 static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
@@ -343,9 +339,8 @@ static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, in
     const unsigned ln_grid = (unsigned)((R + 3) / 4);
     hipLaunchKernelGGL(k_bert_ln<true>, dim3(ln_grid), dim3(256), 0, st, (const float*)nullptr, ids, m->word, m->pos, (int)m->vocab, lengths,
                        (int)max_len, R, m->emb_ln_g, m->emb_ln_b, x);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_bert_ln launch", e);
-    int rc = 0;
+    int rc = launched("k_bert_ln launch");
+    if (rc) return rc;
     for (int l = 0; l < m->n_layers; ++l) {
         const syn_bert_layer& y = m->layer[l];
         GemmArgs g = {};
@@ -355,12 +350,12 @@ static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, in
         const dim3 agrid((unsigned)n_seq, kHeads, (unsigned)((max_len + 63) / 64));
         if (max_len <= 64) hipLaunchKernelGGL(k_bert_attn<4>, agrid, dim3(256), lds, st, (const float*)qkv, lengths, (int)max_len, stride, o);
         else hipLaunchKernelGGL(k_bert_attn<16>, agrid, dim3(256), lds, st, (const float*)qkv, lengths, (int)max_len, stride, o);
-        if ((e = hipGetLastError()) != hipSuccess) return fail("k_bert_attn launch", e);
+        if ((rc = launched("k_bert_attn launch"))) return rc;
         g.a = o; g.w = (const bf16x8*)y.w_out; g.n_frag_cols = kD / 16; g.bias = y.b_out; g.res = x; g.out = tmp; g.ld_out = kD;   // out_lin + residual
         if ((rc = gemm<EPI_RES>(g, kD, st))) return rc;
         hipLaunchKernelGGL(k_bert_ln<false>, dim3(ln_grid), dim3(256), 0, st, (const float*)tmp, (const int32_t*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, 0, lengths, (int)max_len, R, y.ln1_g, y.ln1_b, x);
-        if ((e = hipGetLastError()) != hipSuccess) return fail("k_bert_ln launch", e);
+        if ((rc = launched("k_bert_ln launch"))) return rc;
         g.a = x; g.w = (const bf16x8*)y.w_fc1; g.n_frag_cols = kFF / 16; g.bias = y.b_fc1; g.res = nullptr; g.out = hid; g.ld_out = kFF;  // lin1 + GELU
         if ((rc = gemm<EPI_GELU>(g, kFF, st))) return rc;
         g.a = hid; g.lda = kFF; g.KS = kFF / kKC; g.w = (const bf16x8*)y.w_fc2; g.n_frag_cols = kD / 16; g.bias = y.b_fc2; g.res = x; g.out = tmp;
@@ -368,7 +363,7 @@ static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, in
         if ((rc = gemm<EPI_RES>(g, kD, st))) return rc;
         hipLaunchKernelGGL(k_bert_ln<false>, dim3(ln_grid), dim3(256), 0, st, (const float*)tmp, (const int32_t*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, 0, lengths, (int)max_len, R, y.ln2_g, y.ln2_b, x);
-        if ((e = hipGetLastError()) != hipSuccess) return fail("k_bert_ln launch", e);
+        if ((rc = launched("k_bert_ln launch"))) return rc;
     }
     return 0;
 }

@@ -4,6 +4,7 @@
 // (64 rows x 256 output columns per workgroup, hi + lo bf16 split of both operands: three MFMAs per product) with its epilogue
 // (embedding + pe + tokens, bias, GELU, or bias + residual + LayerNorm); attention is k_tmr_attn (a workgroup per sequence, head and 64 queries).
 // The last layer runs its queries, out_proj, FFN and both LayerNorms on rows 0-1 of each sequence only ("head rows").
+// syn_bert.inc uses this file's tile constants, split8 / load8, the packed-weight layout (k_tmr_pack) and `launched`.
 namespace tmr {
 
 constexpr int kD = 256, kQKV = 768, kFF = 1024, kHeads = 4, kHd = 64, kMaxS = 256;
@@ -40,6 +41,16 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& 
     }
 }
 
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+static int launched(const char* what) {                        // after a launch of this file or syn_bert.inc
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(what, e);
+}
+
 // 256 threads; wave w owns output columns [64 w, 64 w + 64) of the tile, all 64 rows: acc[m tile][n tile].
 template <int EPI>
 __global__ __launch_bounds__(256) void k_tmr_gemm(const GemmArgs a) {
@@ -67,10 +78,8 @@ __global__ __launch_bounds__(256) void k_tmr_gemm(const GemmArgs a) {
     float av[8];
     auto load_a = [&](int k0) {
         const int k = k0 + sg * 8;
-        if (arow && vec) {
-            const float4 p = *reinterpret_cast<const float4*>(arow + k), q = *reinterpret_cast<const float4*>(arow + k + 4);
-            av[0] = p.x; av[1] = p.y; av[2] = p.z; av[3] = p.w; av[4] = q.x; av[5] = q.y; av[6] = q.z; av[7] = q.w;
-        } else {
+        if (arow && vec) load8(arow + k, av);
+        else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) av[j] = (arow && k + j < a.K) ? arow[k + j] : 0.f;
         }
@@ -327,8 +336,7 @@ template <int EPI>
 int gemm(const GemmArgs& a, int n_cols, hipStream_t st) {
     dim3 grid((unsigned)((a.M + kBM - 1) / kBM), (unsigned)(n_cols / kBN));
     hipLaunchKernelGGL(k_tmr_gemm<EPI>, grid, dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_tmr_gemm launch", e);
+    return launched("k_tmr_gemm launch");
 }
 
 static int pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream) {
@@ -337,8 +345,7 @@ static int pack_weight(const float* w, int32_t n, int32_t k, void* out, void* st
     const int ks = (k + 31) / 32;
     const long total = (long)n / 16 * ks * 64;
     hipLaunchKernelGGL(k_tmr_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, ks, (bf16x8*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_tmr_pack launch", e);
+    return launched("k_tmr_pack launch");
 }
 
 static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
@@ -361,26 +368,22 @@ static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, 
     float* o = (float*)ws;                       ws += (size_t)R * kD * 4;
     float* hid = (float*)ws;
 
-    GemmArgs g = {};
-    g.S = S; g.L = max_len;
-    // input Linear (+ ReLU for text) + pe, and the two distribution tokens
+    GemmArgs base = {};                                         // what every Linear of the stack shares: a 256-wide, row-mapped A
+    base.S = S; base.L = max_len; base.lda = kD; base.K = kD; base.KS = kD / 32; base.n_frag_cols = kD / 16; base.a_mapped = 1;
+    GemmArgs g = base;                                          // input Linear (+ ReLU for text) + pe, and the two distribution tokens
     g.a = features; g.lda = m->nfeats; g.K = m->nfeats; g.M = n_seq * max_len; g.a_mapped = 0; g.relu_in = m->relu_in ? 1 : 0; g.rows = ROWS_EMBED;
-    g.w = (const bf16x8*)m->w_in; g.KS = (m->nfeats + 31) / 32; g.n_frag_cols = kD / 16; g.col0 = 0; g.bias = m->b_in;
+    g.w = (const bf16x8*)m->w_in; g.KS = (m->nfeats + 31) / 32; g.bias = m->b_in;
     g.out_f = x; g.pe = m->pe; g.tok_mu = m->mu_token; g.tok_lv = m->logvar_token;
     int rc = gemm<EPI_EMBED>(g, kD, st);
-    if (rc) return rc;
     for (int l = 0; l < SYN_TMR_LAYERS && !rc; ++l) {
         const syn_tmr_layer& y = m->layer[l];
         const bool last = l == SYN_TMR_LAYERS - 1;
-        const int rows = last ? ROWS_HEAD : ROWS_ALL, M = last ? 2 * n_seq : R;
-        GemmArgs q = {};
-        q.S = S; q.L = max_len; q.a = x; q.lda = kD; q.K = kD; q.a_mapped = 1;
-        q.w = (const bf16x8*)y.w_qkv; q.KS = kD / 32; q.n_frag_cols = kQKV / 16; q.bias = y.b_qkv; q.out_h = qkv; q.ld_out = kQKV;
+        GemmArgs q = base;                                     // in_proj of every row
+        q.a = x; q.M = R; q.rows = ROWS_ALL; q.w = (const bf16x8*)y.w_qkv; q.n_frag_cols = kQKV / 16; q.bias = y.b_qkv; q.out_h = qkv; q.ld_out = kQKV;
         if (!last) {
-            q.M = R; q.rows = ROWS_ALL; q.col0 = 0;
             rc = gemm<EPI_BIAS_BF16>(q, kQKV, st);
         } else {                                               // keys / values of every row, queries of rows 0-1
-            q.M = R; q.rows = ROWS_ALL; q.col0 = kD;
+            q.col0 = kD;
             rc = gemm<EPI_BIAS_BF16>(q, 2 * kD, st);
             q.M = 2 * n_seq; q.rows = ROWS_HEAD; q.col0 = 0;
             if (!rc) rc = gemm<EPI_BIAS_BF16>(q, kD, st);
@@ -388,20 +391,17 @@ static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, 
         if (rc) return rc;
         const int q_rows = last ? 2 : S;
         hipLaunchKernelGGL(k_tmr_attn, dim3((unsigned)((q_rows + 63) / 64), kHeads, (unsigned)n_seq), dim3(256), 0, st, qkv, lengths, S, max_len, q_rows, o);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail("k_tmr_attn launch", e);
-        GemmArgs p = {};                                       // out_proj + residual + norm1
-        p.S = S; p.L = max_len; p.a = o; p.lda = kD; p.K = kD; p.M = M; p.a_mapped = 1; p.rows = rows;
-        p.w = (const bf16x8*)y.w_out; p.KS = kD / 32; p.n_frag_cols = kD / 16; p.bias = y.b_out;
-        p.res = x; p.out_f = x; p.ln_g = y.ln1_g; p.ln_b = y.ln1_b;
+        if ((rc = launched("k_tmr_attn launch"))) return rc;
+        GemmArgs t = base;                                     // from here on the last layer runs its head rows only
+        t.rows = last ? ROWS_HEAD : ROWS_ALL; t.M = last ? 2 * n_seq : R;
+        GemmArgs p = t;                                        // out_proj + residual + norm1
+        p.a = o; p.w = (const bf16x8*)y.w_out; p.bias = y.b_out; p.res = x; p.out_f = x; p.ln_g = y.ln1_g; p.ln_b = y.ln1_b;
         if ((rc = gemm<EPI_LN>(p, kD, st))) return rc;
-        GemmArgs f = {};                                       // linear1 + GELU
-        f.S = S; f.L = max_len; f.a = x; f.lda = kD; f.K = kD; f.M = M; f.a_mapped = 1; f.rows = rows;
-        f.w = (const bf16x8*)y.w_fc1; f.KS = kD / 32; f.n_frag_cols = kFF / 16; f.bias = y.b_fc1; f.out_f = hid; f.ld_out = kFF;
+        GemmArgs f = t;                                        // linear1 + GELU
+        f.a = x; f.w = (const bf16x8*)y.w_fc1; f.n_frag_cols = kFF / 16; f.bias = y.b_fc1; f.out_f = hid; f.ld_out = kFF;
         if ((rc = gemm<EPI_GELU>(f, kFF, st))) return rc;
-        GemmArgs s = {};                                       // linear2 + residual + norm2 (the last layer's rows 0 / 1 are mu / logvar)
-        s.S = S; s.L = max_len; s.a = hid; s.lda = kFF; s.K = kFF; s.M = M; s.a_mapped = 0; s.rows = rows;
-        s.w = (const bf16x8*)y.w_fc2; s.KS = kFF / 32; s.n_frag_cols = kD / 16; s.bias = y.b_fc2;
+        GemmArgs s = t;                                        // linear2 + residual + norm2 (the last layer's rows 0 / 1 are mu / logvar)
+        s.a = hid; s.lda = kFF; s.K = kFF; s.KS = kFF / 32; s.a_mapped = 0; s.w = (const bf16x8*)y.w_fc2; s.bias = y.b_fc2;
         s.res = x; s.out_f = x; s.ln_g = y.ln2_g; s.ln_b = y.ln2_b;
         if (last) { s.head_mu = mu; s.head_lv = logvar; }
         rc = gemm<EPI_LN>(s, kD, st);

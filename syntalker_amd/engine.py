@@ -37,6 +37,30 @@ def drop_caches(module) -> dict:
     return {k: v for k, v in module.__dict__.items() if not k.startswith("_syn_")}
 
 
+def derived(module, tensors, build) -> dict:
+    """The module's cache of what `build` derives from `tensors`: `module.__dict__["_syn_packed"]` while its "ver" is their `weights_key`, else a
+    fresh {"ver", "keep": [], "ws": {}} that `build(p)` fills ("keep": the tensors raw pointers refer to, "ws": per-shape workspaces).  It
+    replaces the module's cache only once `build` has returned: a `build` that raises leaves none behind."""
+    ver = weights_key(tensors)
+    p = module.__dict__.get("_syn_packed")
+    if p is None or p["ver"] != ver:
+        p = {"ver": ver, "keep": [], "ws": {}}
+        build(p)
+        module.__dict__["_syn_packed"] = p
+    return p
+
+
+def workspace(cache: dict, key, nbytes, device) -> torch.Tensor:
+    """The uint8 workspace cached under `key`; a miss on a cache that already holds more than four clears it, then allocates `nbytes` (an int,
+    or a callable that gives one and runs on a miss only)."""
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) > 4:
+            cache.clear()
+        ws = cache[key] = torch.empty(nbytes() if callable(nbytes) else nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 def _require_cuda(t: torch.Tensor, what: str):
     if not t.is_cuda:
         raise _lib.SynHipError(

@@ -248,16 +248,15 @@ class VAESKConv(nn.Module):
     def packed(self):
         """syn_skel_model of this module: per layer the masked, block-sparse weight fragments of both branches, the biases, GroupNorm affine
         and output pooling as gather lists.  Rebuilt when an encoder parameter changes (version counters, `engine.weights_key`) or moves."""
-        ver = engine.weights_key(self._encoder_tensors())
-        p = self.__dict__.get("_syn_packed")
-        if p is not None and p["ver"] == ver:
-            return p
+        return engine.derived(self, self._encoder_tensors(), self._pack)
+
+    def _pack(self, p: dict):
         dev = self.encoder.layers[0][0].shortcut.weight.device
         if dev.type != "cuda":
             raise _lib.SynHipError("VAESKConv runs on the HIP kernels only: move the module to the GPU (no CPU fallback)")
         lib = _lib.load()
         st = _lib.current_stream(dev)
-        keep, kept = [], []
+        keep, kept = p["keep"], []
         m = _lib.SynSkelModel()
         for i, seq in enumerate(self.encoder.layers):
             blk = seq[0]
@@ -290,8 +289,7 @@ class VAESKConv(nn.Module):
             keep += [w, mk, ws, ms, off, chunk, out, bias, g, b, src, sw]
             m.layer[i] = _lib.SynSkelLayer(out.data_ptr(), off.data_ptr(), chunk.data_ptr(), bias.data_ptr(), g.data_ptr(), b.data_ptr(),
                                            src.data_ptr(), sw.data_ptr(), cin, cout, src.shape[0], 0)
-        self._syn_packed = {"ver": ver, "model": m, "keep": keep, "kept": kept, "ws": {}}
-        return self._syn_packed
+        p.update(model=m, kept=kept)
 
     @staticmethod
     def _pool_gather(blk, cout: int, dev):
@@ -342,13 +340,9 @@ class VAESKConv(nn.Module):
         p = self.packed()
         dev = inputs.device
         x = inputs.detach().float().contiguous()
-        key = (b, n)
-        if key not in p["ws"]:
-            if len(p["ws"]) > 4:
-                p["ws"].clear()
-            p["ws"][key] = torch.empty(workspace_bytes([q["cout"] for q in self.plan], b, n), dtype=torch.uint8, device=dev)
+        ws = engine.workspace(p["ws"], (b, n), lambda: workspace_bytes([q["cout"] for q in self.plan], b, n), dev)
         out = torch.empty(b, n // 16, self.plan[-1]["out_width"], device=dev)
-        _lib.check(_lib.load().syn_skel_encode(C.byref(p["model"]), x.data_ptr(), b, n, p["ws"][key].data_ptr(), out.data_ptr(),
+        _lib.check(_lib.load().syn_skel_encode(C.byref(p["model"]), x.data_ptr(), b, n, ws.data_ptr(), out.data_ptr(),
                                                _lib.current_stream(dev)), "syn_skel_encode")
         return out
 

@@ -98,16 +98,15 @@ class RVQVAE(nn.Module):
     def packed(self):
         """syn_vq_model of this module: fragment-packed conv weights, padded biases, codebook views.  Rebuilt when a
         parameter changes or moves (`engine.weights_key`)."""
-        ver = engine.weights_key(list(self.parameters()) + list(self.buffers()))
-        p = self.__dict__.get("_syn_packed")
-        if p is not None and p["ver"] == ver:
-            return p
+        return engine.derived(self, list(self.parameters()) + list(self.buffers()), self._pack)
+
+    def _pack(self, p: dict):
         sd = self.state_dict()
         dev = sd["decoder.model.0.weight"].device
         if dev.type != "cuda":
             raise _lib.SynHipError("RVQVAE runs on the HIP kernels only: move the module to the GPU (no CPU fallback)")
         _lib.load()
-        vm, keep = _lib.SynVqModel(), []
+        vm, keep = _lib.SynVqModel(), p["keep"]
         vm.pose_dim = self.input_width
         for arr, specs in ((vm.enc, self._enc), (vm.dec, self._dec)):
             for i, (key, cin, cout, taps, stride, dil, pad) in enumerate(specs):
@@ -121,17 +120,10 @@ class RVQVAE(nn.Module):
         cbt = cb.transpose(1, 2).contiguous()
         cc = torch.sum(cbt ** 2, dim=1).contiguous()                        # quantizer.py:66: sum(k_w**2, dim=0)
         vm.codebooks, vm.codebooks_t, vm.code_sq = cb.data_ptr(), cbt.data_ptr(), cc.data_ptr()
-        self._syn_packed = {"ver": ver, "model": vm, "keep": keep, "cb": cb, "cbt": cbt, "cc": cc, "ws": {}}
-        return self._syn_packed
+        p.update(model=vm, cb=cb, cbt=cbt, cc=cc)
 
     def _workspace(self, p, clips, t_pose, dev):
-        key = (clips, t_pose)
-        if key not in p["ws"]:
-            if len(p["ws"]) > 4:
-                p["ws"].clear()
-            nbytes = _lib.load().syn_vq_workspace_bytes(clips, t_pose, self.input_width)
-            p["ws"][key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return p["ws"][key]
+        return engine.workspace(p["ws"], (clips, t_pose), lambda: _lib.load().syn_vq_workspace_bytes(clips, t_pose, self.input_width), dev)
 
     def _quantize(self, lat):
         """lat (N, T', 512) fp32 -> quantised fp32 rows, indices (N, T', 6), commit loss, perplexity (quantiser alone)."""

@@ -47,14 +47,10 @@ class _EvalOnly(nn.Module):
         return dev
 
     def _cached(self, build):
-        ver = engine.weights_key(list(self.parameters()))
-        p = self.__dict__.get("_syn_packed")
-        if p is None or p["ver"] != ver:
-            dev = self._device()
-            p = {"ver": ver, "keep": [], "ws": {}, "idx": {}}
-            build(p, dev)
-            self._syn_packed = p
-        return p
+        def fill(p):
+            p["idx"] = {}
+            build(p, self._device())
+        return engine.derived(self, list(self.parameters()), fill)
 
 
 def _pack(p: dict, w: torch.Tensor, conv_cin: int = 0, layout: int = 0) -> int:
@@ -117,16 +113,13 @@ def _lengths(p: dict, kind: int, lens: np.ndarray, dev):
 
 
 def _workspace(p: dict, kind: int, n: int, length: int, dev) -> torch.Tensor:
-    key = (kind, n, length)
-    if key not in p["ws"]:
-        if len(p["ws"]) > 4:
-            p["ws"].clear()
+    def nbytes():
         size = int(_lib.load().syn_t2m_workspace_bytes(n, length, kind))
         if size < 0:
             raise ValueError(f"T2M evaluator: {n} sequences of {length} outside what the library takes "
                              f"(at most {_lib.SYN_T2M_MAX_FRAMES} frames / tokens)")
-        p["ws"][key] = torch.empty(size, dtype=torch.uint8, device=dev)
-    return p["ws"][key]
+        return size
+    return engine.workspace(p["ws"], (kind, n, length), nbytes, dev)
 
 
 class MovementConvEncoder(_EvalOnly):

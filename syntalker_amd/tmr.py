@@ -93,15 +93,14 @@ class _TmrStack(nn.Module):
     def packed(self):
         """syn_tmr_model of this module: fragment-packed weights and views of the biases.  Rebuilt when a parameter changes (version
         counters, `engine.weights_key`) or moves."""
-        ver = engine.weights_key(self._stack_tensors())
-        p = self.__dict__.get("_syn_packed")
-        if p is not None and p["ver"] == ver:
-            return p
+        return engine.derived(self, self._stack_tensors(), self._pack)
+
+    def _pack(self, p: dict):
         if not self.mu_token.is_cuda:
             raise _lib.SynHipError(f"{type(self).__name__} runs on the HIP kernels only: move the module to the GPU (no CPU fallback)")
         lib = _lib.load()
         st = _lib.current_stream(self.mu_token.device)
-        keep = []
+        keep = p["keep"]
 
         def pack(w):
             w = w.detach().float().contiguous()
@@ -125,21 +124,12 @@ class _TmrStack(nn.Module):
             m.layer[i] = _lib.SynTmrLayer(pack(a.in_proj_weight), vec(a.in_proj_bias), pack(a.out_proj.weight), vec(a.out_proj.bias),
                                           vec(y.norm1.weight), vec(y.norm1.bias), pack(y.linear1.weight), vec(y.linear1.bias),
                                           pack(y.linear2.weight), vec(y.linear2.bias), vec(y.norm2.weight), vec(y.norm2.bias))
-        self._syn_packed = {"ver": ver, "model": m, "keep": keep, "ws": {}, **self._pack_more(pack, vec)}
-        return self._syn_packed
+        p.update(model=m, **self._pack_more(pack, vec))
 
     def _pack_more(self, pack, vec) -> dict:
         """Further entries of the packed() cache a subclass derives from its weights (`pack`: a Linear's weight -> fragment pointer, `vec`: fp32
         pointer; both keep their tensors alive with the cache)."""
         return {}
-
-    @staticmethod
-    def _workspace(cache: dict, key, nbytes, device):
-        if key not in cache:
-            if len(cache) > 4:
-                cache.clear()
-            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return cache[key]
 
     def _encode(self, x: torch.Tensor, lengths):
         """x (B, L, nfeats) on the module's device, lengths None (all L) or a device int tensor (B,) -> (mu, logvar) fp32 (B, 256)."""
@@ -158,7 +148,7 @@ class _TmrStack(nn.Module):
             lengths = lengths.to(device=x.device, dtype=torch.int32).contiguous()
             if lengths.shape != (b,):
                 raise ValueError(f"lengths: expected ({b},), got {tuple(lengths.shape)}")
-        ws = self._workspace(p["ws"], (b, L), workspace_bytes(b, L), x.device)
+        ws = engine.workspace(p["ws"], (b, L), workspace_bytes(b, L), x.device)
         mu = torch.empty(b, D, device=x.device)
         logvar = torch.empty(b, D, device=x.device)
         _lib.check(_lib.load().syn_tmr_encode(C.byref(m), x.data_ptr(), b, L, _lib.ptr(lengths), ws.data_ptr(),
@@ -320,7 +310,7 @@ class DistilbertActorAgnosticEncoder(_TmrStack):
             raise ValueError(f"lengths: expected ({b},), got {tuple(lengths.shape)}")
         ids = ids.to(torch.int32).contiguous()
         lengths = lengths.to(torch.int32).contiguous()
-        ws = self._workspace(p["bert_ws"], (b, L), bert_workspace_bytes(b, L), dev)
+        ws = engine.workspace(p["bert_ws"], (b, L), bert_workspace_bytes(b, L), dev)
         hidden = torch.empty(b, L, BERT_D, device=dev)
         _lib.check(_lib.load().syn_bert_encode(C.byref(p["bert"]), ids.data_ptr(), b, L, lengths.data_ptr(), ws.data_ptr(), hidden.data_ptr(),
                                                _lib.current_stream(dev)), "syn_bert_encode")

@@ -578,3 +578,56 @@ def test_small_gradients_move_into_bound_bucket_buffers():
         assert grads3[0].data_ptr() != bucket[0:8].data_ptr() and torch.equal(bucket[0:8], dgb[0])
     finally:
         training.unbind_grad_buffers(torch.nn.ModuleList([bn, conv]))
+
+
+def test_derived_cache_follows_the_weights_key():
+    """engine.derived on a CPU nn.Linear (`build` only counts calls): a hit, then a rebuild for each kind of write `weights_key` sees, and no
+    cache left behind by a `build` that raises."""
+    lin = torch.nn.Linear(3, 2)
+    tensors = lambda: list(lin.parameters())
+    calls = []
+
+    def build(p):
+        assert set(p) == {"ver", "keep", "ws"} and p["keep"] == [] and p["ws"] == {}
+        calls.append(p)
+
+    p = engine.derived(lin, tensors(), build)
+    assert len(calls) == 1 and lin.__dict__["_syn_packed"] is p and p["ver"] == engine.weights_key(tensors())
+    assert engine.derived(lin, tensors(), build) is p and len(calls) == 1              # a second call hits
+    with torch.no_grad():
+        lin.weight.add_(1)                                                            # an in-place write
+    assert engine.derived(lin, tensors(), build) is calls[1] and len(calls) == 2
+    torch.autograd.graph.increment_version([lin.weight])                              # a writer PyTorch cannot see
+    assert engine.derived(lin, tensors(), build) is calls[2] and len(calls) == 3
+    lin.weight.data = lin.weight.data.clone()                                         # a new address
+    assert engine.derived(lin, tensors(), build) is calls[3] and len(calls) == 4
+    assert engine.derived(lin, tensors(), build) is calls[3] and len(calls) == 4
+    assert not any(k.startswith("_syn_") for k in engine.drop_caches(lin)) and "_syn_packed" in lin.__dict__
+
+    other = torch.nn.Linear(3, 2)
+
+    def broken(p):
+        raise RuntimeError("no device")
+
+    with pytest.raises(RuntimeError, match="no device"):
+        engine.derived(other, list(other.parameters()), broken)
+    assert "_syn_packed" not in other.__dict__
+    n = len(calls)
+    engine.derived(other, list(other.parameters()), build)                           # the next call builds again
+    assert len(calls) == n + 1 and other.__dict__["_syn_packed"] is calls[-1]
+
+
+def test_workspace_cache_keeps_at_most_five_shapes():
+    cache = {}
+    first = engine.workspace(cache, (1, 1), 16, "cpu")
+    assert first.dtype == torch.uint8 and first.numel() == 16 and first.device.type == "cpu"
+    assert engine.workspace(cache, (1, 1), 16, "cpu") is first
+
+    def never():
+        raise AssertionError("the size is asked for on a miss only")
+
+    assert engine.workspace(cache, (1, 1), never, "cpu") is first                      # a callable nbytes is not called on a hit
+    for i in range(2, 7):                                                             # six distinct keys in all
+        assert engine.workspace(cache, (i, 1), lambda: 8 * i, "cpu").numel() == 8 * i
+        assert len(cache) <= 5
+    assert (1, 1) not in cache and (6, 1) in cache
