@@ -144,6 +144,21 @@ int32_t syn_prefers_fragment_order(int32_t n_clips, int32_t n_variants);
  * variants of a small guided batch were dealt to different XCDs), or the 42-kernel A/B path (reserved = 1). */
 int syn_denoise_step(const syn_model* model, const syn_step* step, void* stream);
 
+/* In-painting (diffusion/gaussian_diffusion.py:316-320, y['inpainting_mask'] / y['inpainted_motion']): the model's x0_hat is
+ * replaced by `known` wherever `keep` is set - after the guidance combination, before the update x_next = c_x0*x0_hat + c_xt*x_t +
+ * sigma*noise, and before pred_x0 is written (the reference returns the blended pred_xstart).  Both tensors are token-major like x_t and,
+ * like it, read four consecutive channels at a time: keep must be 4-byte aligned and known 16-byte aligned. */
+typedef struct syn_edit {
+    const uint8_t* keep;    /* [B*32][1536] nonzero = keep the known value                      */
+    const float*   known;   /* [B*32][1536] fp32, the values to keep                            */
+} syn_edit;
+
+/* syn_denoise_step with the blend above in the output stage of whichever token-major kernel runs the step; the same contract
+ * (nothing allocated or synchronised, graph-capturable).  edit == NULL, or both of its pointers NULL: exactly syn_denoise_step.
+ * Refused: exactly one of keep / known NULL; x_fragment_order = 1 or reserved = 5 (the wave-per-sequence kernel takes no edit, so a
+ * batch with an edit runs token-major at every size).  syn_denoise_steps has no such variant. */
+int syn_denoise_step_edit(const syn_model* model, const syn_step* step, const syn_edit* edit, void* stream);
+
 /* Loop helper: fills t_coef[0..n_t_coef) with sched[2i] and t_model[0..n_t_model) with sched[2i + 1], i = *counter, then
  * advances *counter - a whole p_sample_loop iteration (gaussian_diffusion.py:714-739) becomes one graph replay
  * (this launch + syn_denoise_step) with no host work in between. */

@@ -7,6 +7,7 @@ Fréchet statistic of the sampled latents against reference statistics.
     python scripts/sample_from_config.py configs.yaml [--seconds 8] [--takes 4] [--ddim] [--seed 1]
                                          [--random-init] [--inputs in.npz] [--ref-stats ref.npz] [--out out.npz]
                                          [--upper-prompt TEXT] [--hands-prompt TEXT] [--lower-prompt TEXT]
+                                         [--keep-from TAKE.npz [--keep-parts upper,hands,lower] [--keep-frames a:b]]
 
 --random-init   ignore the checkpoint / statistics paths of the YAML and use the name-keyed synthetic weights (there is no
                 network for the reference's checkpoints here); without it every configured path must exist.
@@ -17,6 +18,14 @@ Fréchet statistic of the sampled latents against reference statistics.
                 encoder (tmr.build_encoders: `tmr_base_path`, `tmr_text_model_path` or ./ckpt/distilbert-base-uncased) and the per-part
                 style dict drives TwoClassifierFreeSampleModel_Bodypart; a part without a prompt gets the zero vector there.  Without
                 any prompt the denoiser samples unguided with a zero style vector, as before.
+--keep-from / --keep-parts / --keep-frames
+                motion editing (in-painting, `longform.sample_long(edit=...)`; BEAT-X configuration): TAKE.npz holds the recorded take - pose
+                (B, n, 165) axis-angle, optionally trans_v (B, n, 3) root velocity and mask_upper / mask_hands / mask_lower (0/1 over the 165
+                channels).  A real take should carry its mask_* arrays - the reference's joint lists (dataloaders/data_tools.py, beat_smplx_upper /
+                _hands / _lower); without them the stand-in masks of `synth.synth_joint_masks` are used, which have the reference's joint
+                counts per part but are not guaranteed to be its joints.  It goes through `poses.encode_take` to the sampler's
+                latents; the body parts named by --keep-parts (all frames) and the latent frames a:b (half-open, pose frame / 4; all channels)
+                are kept from it and the rest is generated.
 """
 import argparse
 import json
@@ -46,6 +55,32 @@ def prompt_styles(args, prompts: dict, dev, random_init: bool) -> dict:
         return {f"{part}_mask": (None if prompts[part] is None else text(prompts[part]).loc) for part in PROMPT_PARTS}
 
 
+def edit_from_take(a, args, s, dev, n: int, batch: int, squeeze: int):
+    """(known_latent, keep) of --keep-from / --keep-parts / --keep-frames for `sample_long(edit=...)`."""
+    from syntalker_amd import poses
+    if config.is_h3d(args):
+        raise SystemExit("--keep-from takes 165-channel SMPL-X poses: the BEAT-X configuration")
+    z = np.load(a.keep_from)
+    pose = torch.from_numpy(z["pose"]).float().to(dev)
+    if pose.shape[0] != batch or pose.shape[1] < n:
+        raise SystemExit(f"--keep-from: pose is {tuple(pose.shape)}, the run has {batch} takes of {n} pose frames")
+    pose = pose[:, :n - n % squeeze]
+    trans_v = None
+    if s.use_trans:
+        trans_v = torch.from_numpy(z["trans_v"]).float().to(dev)[:, :pose.shape[1]] if "trans_v" in z else torch.zeros(*pose.shape[:2], 3, device=dev)
+    masks = synth.synth_joint_masks()
+    masks.update({k: z[f"mask_{k}"] for k in masks if f"mask_{k}" in z})
+    stats = None if s.trans_mean is None else (s.trans_mean, s.trans_std)
+    with torch.no_grad():
+        known = poses.encode_take(pose, trans_v, s.vq["upper"], s.vq["hands"], s.vq["lower"], masks, None, stats, s.latent_scale)["latent_in"]
+    parts = tuple(p for p in (a.keep_parts or "").split(",") if p)
+    frames = None
+    if a.keep_frames:
+        lo, hi = a.keep_frames.split(":")
+        frames = (int(lo or 0), int(hi) if hi else known.shape[1])
+    return known, longform.keep_mask(known.shape[1], parts, frames)
+
+
 def main(argv=None) -> dict:
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
@@ -59,7 +94,14 @@ def main(argv=None) -> dict:
     ap.add_argument("--out")
     for part in PROMPT_PARTS:
         ap.add_argument(f"--{part}-prompt")
+    ap.add_argument("--keep-from")
+    ap.add_argument("--keep-parts")
+    ap.add_argument("--keep-frames")
     a = ap.parse_args(argv)
+    if (a.keep_parts or a.keep_frames) and not a.keep_from:
+        raise SystemExit("--keep-parts / --keep-frames need --keep-from: the take to keep them from")
+    if a.keep_from and not (a.keep_parts or a.keep_frames):
+        raise SystemExit("--keep-from needs --keep-parts and / or --keep-frames: what to keep of the take")
     over = {k: None for k in PATH_KEYS} if a.random_init else {}
     args = config.load_args(a.config, **over)
     s = config.build_sampler(args)
@@ -91,9 +133,10 @@ def main(argv=None) -> dict:
         from syntalker_amd.guidance import TwoClassifierFreeSampleModel_Bodypart
         model = TwoClassifierFreeSampleModel_Bodypart(s.model)
         y_extra = {"style_feature": prompt_styles(args, prompts, dev, a.random_init)}
+    edit = edit_from_take(a, args, s, dev, n, word.shape[0], squeeze) if a.keep_from else None
     torch.cuda.synchronize(); t0 = time.perf_counter()
     lat = longform.sample_long(diffusion, model, audio, word, seed_lat, n, pose_length=pose_length, pre_frames=pre, squeeze=squeeze,
-                               use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra)
+                               use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra, edit=edit)
     torch.cuda.synchronize(); t1 = time.perf_counter()
     out = longform.decode_take(lat, s.vq["upper"], s.vq["hands"], s.vq["lower"], s.latent_scale, use_trans=s.use_trans,
                                trans_mean=s.trans_mean, trans_std=s.trans_std)
@@ -103,6 +146,10 @@ def main(argv=None) -> dict:
            "latents": list(lat.shape), "poses": {k: (None if v is None else list(v.shape)) for k, v in out.items()},
            "prompts": {k: v for k, v in prompts.items() if v is not None},
            "finite": bool(all(v is None or bool(torch.isfinite(v).all()) for v in out.values()))}
+    if edit is not None:
+        kept = edit[1].to(lat.device)[:lat.shape[1]].expand(lat.shape)
+        rep["edit"] = {"path": diffusion.last_path, "kept_fraction": round(float(kept.float().mean()), 4),
+                       "kept_exact": bool(torch.equal(lat[kept], edit[0][:, :lat.shape[1]][kept]))}
     if a.ref_stats:
         z = np.load(a.ref_stats)
         emb = metrics.latent_embedding(lat.float().cpu().numpy(), dim=int(z["mu"].shape[0]))

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SYN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsyn_
 
 SYN_LAYERS = 8
 ABI_VERSION = 9             # include/syn_hip.h SYN_ABI_VERSION: a library built from other sources is refused at load time
-EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_steps", "syn_denoise_step_profile", "syn_pack_weight", "syn_pack_weight_t", "syn_to_token_major",
+EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_step_edit", "syn_denoise_steps", "syn_denoise_step_profile", "syn_pack_weight", "syn_pack_weight_t", "syn_to_token_major",
            "syn_from_token_major", "syn_axpby_rows", "syn_randn", "syn_linear", "syn_linear_pair", "syn_linear_and_pack", "syn_linear_res", "syn_linear_gelu", "syn_opt_blocks", "syn_opt_sqnorm", "syn_opt_scalars", "syn_opt_adam", "syn_test_gemm", "syn_test_attention", "syn_test_handoff",
            "syn_wav_encode", "syn_wav_workspace_bytes", "syn_wav_out_frames", "syn_linear_bwd_prep", "syn_embedding_wgrad", "syn_pack_weights", "syn_bn_chunks", "syn_bn_act_fwd", "syn_bn_act_bwd", "syn_bn_sums", "syn_bn_act_apply", "syn_bn_bwd_sums", "syn_bn_act_bwd_apply", "syn_conv1d_train_fwd", "syn_conv1d_train_fwd_tiles", "syn_conv1d_pack_split", "syn_conv1d_pack_split_many", "syn_conv1d_pack_bytes", "syn_conv1d_train_wgrad", "syn_conv1d_train_wgrad_pair", "syn_conv1d_wgrad_shares", "syn_conv1d_first_parts", "syn_conv1d_first_fwd", "syn_conv1d_first_wgrad", "syn_conv1d_first_wgrad_tail", "syn_conv1d_first_wgrad_bn_lin", "syn_cond_encode",
            "syn_vq_conv1d", "syn_vq_quantize", "syn_vq_quantize_groups", "syn_vq_codes",
@@ -73,6 +73,11 @@ class SynStep(C.Structure):
                 ("ws_h", vp), ("ws_xn", vp), ("ws_q", vp), ("ws_k", vp), ("ws_vt", vp), ("ws_o", vp),
                 ("ws_hid", vp), ("ws_hc", vp), ("ws_sync", vp), ("ws_x0v", vp), ("ws_xch", vp),
                 ("x_fragment_order", i32), ("cfg_w_clip_stride", i32)]
+
+
+class SynEdit(C.Structure):
+    """include/syn_hip.h syn_edit: in-painting operands of syn_denoise_step_edit, token-major like x_t."""
+    _fields_ = [("keep", vp), ("known", vp)]
 
 
 SYN_OPT_MAX = 64
@@ -208,6 +213,7 @@ def load():
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib.syn_last_error.restype = C.c_char_p
     lib.syn_denoise_step.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), vp]
+    lib.syn_denoise_step_edit.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), C.POINTER(SynEdit), vp]
     lib.syn_denoise_steps.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), C.c_int32, C.c_int32, C.c_int32, vp]
     lib.syn_denoise_step_profile.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), vp, vp, vp]
     lib.syn_pack_weight.argtypes = [vp, i32, i32, vp, vp]

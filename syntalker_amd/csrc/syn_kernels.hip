@@ -66,6 +66,8 @@ struct GArgs {
     const float* Xt; const float* noise; const float* coef; const int* t_coef;
     float* Xn; __bf16* Xnb; float* X0;
     const unsigned long long* rng;   // {seed, first_clip}: draw the noise in the epilogue, stream id = the clip's t_coef
+    // in-painting (syn_denoise_step_edit): x0 = keep ? known : x0 ahead of the update; both token-major like Xt, both NULL = no edit
+    const unsigned char* keep; const float* known;
     // plain fp32 output (unit tests)
     float* Yf; int ldyf;
     int ablate;   // diagnostics (syn_test_gemm only): 1 = weights loaded once, 2 = activations staged once, 4 = no store
@@ -90,6 +92,28 @@ __device__ __forceinline__ void rotary4(f32x4& u, f32x4& w, const f32x4 cs, cons
 __device__ __forceinline__ bf16x4 to_bf16x4(f32x4 v) {
     bf16x4 r;
     r[0] = (__bf16)v[0]; r[1] = (__bf16)v[1]; r[2] = (__bf16)v[2]; r[3] = (__bf16)v[3];
+    return r;
+}
+
+// In-painting blend of the reference's p_mean_variance (diffusion/gaussian_diffusion.py:316-320) on four consecutive channels of one
+// token: x0 = keep ? known : x0.  Callers test `keep` for null first (wave-uniform), so a step without an edit issues none of these loads.
+__device__ __forceinline__ f32x4 edit_x0(const unsigned char* __restrict__ keep, const float* __restrict__ known, const size_t off, f32x4 x0) {
+    const uchar4 k = *reinterpret_cast<const uchar4*>(keep + off);
+    const f32x4 kn = *reinterpret_cast<const f32x4*>(known + off);
+    x0[0] = k.x ? kn[0] : x0[0]; x0[1] = k.y ? kn[1] : x0[1]; x0[2] = k.z ? kn[2] : x0[2]; x0[3] = k.w ? kn[3] : x0[3];
+    return x0;
+}
+
+// c0 x0 + c1 x_t with the roundings hipcc gives the plain expression `x0 * c0 + xt * c1` in the output stages: fma(x0, c0, xt * c1), the second
+// product rounded on its own.  Written out for k_stack's EDIT instances: behind the blend's select the compiler multiplies both arms by c0 first
+// and fuses the OTHER product, and the entries that are not kept would differ from the plain step's in the last bit.
+// Only this side is pinned: the plain instances keep the expression, so that they compile to what they were.  Their contraction was read from
+// the ISA of ROCm 7.2's hipcc (AMD clang 22.0.0git, roc-7.2.0); should a compiler contract it differently, tests/test_gpu_edit.py's bit-equality
+// checks fail with no change here, and the fix is to write the plain side with update_pinned's operations too.
+__device__ __forceinline__ f32x4 update_pinned(const f32x4 x0, const f32x4 xt, const float c0, const float c1) {
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(x0[e], c0, __fmul_rn(xt[e], c1));
     return r;
 }
 
@@ -563,7 +587,8 @@ __device__ __forceinline__ void gemm_body(const GArgs& a, const int bx, const in
             for (int nf = 0; nf < 4; ++nf) {
                 const int n = ncol + nf * 16 + g * 4;
                 const size_t off = (size_t)m * SYN_C + n;
-                const f32x4 x0 = acc[nf][mf] + *reinterpret_cast<const f32x4*>(a.bias + n);
+                f32x4 x0 = acc[nf][mf] + *reinterpret_cast<const f32x4*>(a.bias + n);
+                if (a.keep) x0 = edit_x0(a.keep, a.known, off, x0);
                 const f32x4 xt = *reinterpret_cast<const f32x4*>(a.Xt + off);
                 f32x4 xn = x0 * cf[0] + xt * cf[1];
                 if (a.noise) xn = xn + *reinterpret_cast<const f32x4*>(a.noise + off) * cf[2];
@@ -890,7 +915,9 @@ __device__ __forceinline__ void ln_to_lds(f32x4 (&h)[4][MT / 16], const float* _
     }
 }
 
-template <int MT, int TP = 0>       // TP: members per tile in the tile-split mode (0 = off, 2, 4)
+// EDIT: the output stage blends the in-painting operands in (out.keep / out.known).  A template flag, not the wave-uniform null test of
+// the other output stages: k_stack<64> sits at 256 VGPRs, and the test alone cost it 16 bytes of scratch per lane in steps without an edit.
+template <int MT, int TP = 0, bool EDIT = false>       // TP: members per tile in the tile-split mode (0 = off, 2, 4)
 __global__ __launch_bounds__(kThreads) void k_stack(const SArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MF = MT / 16;
@@ -1288,7 +1315,10 @@ __global__ __launch_bounds__(kThreads) void k_stack(const SArgs a) {
             float* const T = reinterpret_cast<float*>(RB) + wave * (16 * 68);
             const bool nz_buf = a.out.noise != nullptr, nz_rng = !nz_buf && a.out.rng != nullptr;
             const f32x4 bias = *reinterpret_cast<const f32x4*>(a.out.bias + ncol);
-            f32x4 xt[2][4];
+            // (EDIT, 64-row tiles: x_t of a row tile is requested when the tile comes up, not one ahead - the blend's operands take the registers
+            //  of the second slot.  One ahead this instance spills 15 VGPRs / 44 B of scratch, this way 9 / 32 B; the plain one 6 / 28 B.)
+            constexpr bool AHEAD = !(EDIT && MT == 64);
+            f32x4 xt[AHEAD ? 2 : 1][4];
             auto fetch = [&](int mf, int slot) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -1296,10 +1326,11 @@ __global__ __launch_bounds__(kThreads) void k_stack(const SArgs a) {
                     xt[slot][i] = *reinterpret_cast<const f32x4*>(a.out.Xt + (size_t)m * SYN_C + ncol);
                 }
             };
-            fetch(0, 0);
+            if constexpr (AHEAD) fetch(0, 0);
 #pragma unroll
             for (int mf = 0; mf < MF; ++mf) {
-                if (mf + 1 < MF) fetch(mf + 1, (mf + 1) & 1);
+                if constexpr (!AHEAD) fetch(mf, 0);
+                else if (mf + 1 < MF) fetch(mf + 1, (mf + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int nf = 0; nf < 4; ++nf) *reinterpret_cast<f32x4*>(T + lr * 68 + nf * 16 + g * 4) = acc[nf][mf];
@@ -1315,8 +1346,11 @@ __global__ __launch_bounds__(kThreads) void k_stack(const SArgs a) {
                     const int m = m0 + mf * 16 + i * 4 + er;
                     const bool ok = m < a.M;
                     const size_t off = (size_t)m * SYN_C + ncol;
-                    const f32x4 x0 = av[i] + bias;
-                    f32x4 xn = x0 * cf[0] + xt[mf & 1][i] * cf[1];
+                    f32x4 x0 = av[i] + bias;
+                    if constexpr (EDIT) x0 = edit_x0(a.out.keep, a.out.known, ok ? off : 0, x0);
+                    f32x4 xn;
+                    if constexpr (EDIT) xn = update_pinned(x0, xt[AHEAD ? mf & 1 : 0][i], cf[0], cf[1]);
+                    else xn = x0 * cf[0] + xt[mf & 1][i] * cf[1];
                     if (nz_buf) xn = xn + *reinterpret_cast<const f32x4*>(a.out.noise + (ok ? off : 0)) * cf[2];
                     else if (nz_rng) xn = xn + randn4(a.out.rng[0], (uint64_t)tc, (a.out.rng[1] * (uint64_t)(SYN_T * SYN_C) + off) >> 2) * cf[2];
                     if (ok) {
@@ -1367,6 +1401,7 @@ struct UArgs {
     const float* X0v; const float* w; int w_stride; int V, B;
     const float* Xt; const float* noise; const unsigned long long* rng; const float* coef; const int* t_coef;
     float* Xn; __bf16* Xnb; float* X0;
+    const unsigned char* keep; const float* known;      // in-painting, as in GArgs
 };
 __global__ void k_guided_update(const UArgs a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1378,6 +1413,7 @@ __global__ void k_guided_update(const UArgs a) {
     f32x4 x0 = {0.f, 0.f, 0.f, 0.f};
     for (int v = 0; v < a.V; ++v)
         x0 = x0 + *reinterpret_cast<const f32x4*>(a.X0v + (size_t)v * a.B * SYN_T * SYN_C + off) * a.w[(size_t)clip * a.w_stride + blk * a.V + v];
+    if (a.keep) x0 = edit_x0(a.keep, a.known, off, x0);
     const int tc = a.t_coef[clip];
     const f32x4 cf = *reinterpret_cast<const f32x4*>(a.coef + (size_t)tc * 4);
     f32x4 xn = x0 * cf[0] + *reinterpret_cast<const f32x4*>(a.Xt + off) * cf[1];
@@ -1657,6 +1693,22 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
         if (!(mt == 32 || (mt == 64 && a.tp == 2)) || !a.sync || !a.xch) return fail_msg("stack: the tile-split mode needs 32-row tiles (or 64-row tiles split in two), ws_sync and ws_xch");
         grid.x = lat::kGroups * a.tp * ((a.tp_tiles + lat::kGroups - 1) / lat::kGroups);    // whole groups on every XCD
         if (grid.x > 256) return fail_msg("stack: the tensor-parallel mode needs all its workgroups resident (<= 256)");
+    }
+    if (a.out.keep) {          // in-painting: the EDIT instances (32-row tiles whole or split, 64-row tiles whole)
+        static OncePerDevice once_ed;
+        if (once_ed.first()) {
+            allow_lds(k_stack<64, 0, true>, 64 * 2048 + 4096); allow_lds(k_stack<32, 0, true>, 32 * 2048 + 4096);
+            allow_lds(k_stack<32, 2, true>, 32 * 2048 + 4096); allow_lds(k_stack<32, 4, true>, 32 * 2048 + 4096);
+        }
+        if (a.tp > 1 && mt != 32) return fail_msg("stack: an edit takes split tiles of 32 rows only");
+        if (a.tp == 4) hipLaunchKernelGGL((k_stack<32, 4, true>), grid, block, 32 * 2048 + 4096, s, a);
+        else if (a.tp == 2) hipLaunchKernelGGL((k_stack<32, 2, true>), grid, block, 32 * 2048 + 4096, s, a);
+        else if (a.tp > 1) return fail_msg("stack: tile split over 2 or 4 workgroups only");
+        else if (mt == 64) hipLaunchKernelGGL((k_stack<64, 0, true>), grid, block, 64 * 2048 + 4096, s, a);
+        else if (mt == 32) hipLaunchKernelGGL((k_stack<32, 0, true>), grid, block, 32 * 2048 + 4096, s, a);
+        else return fail_msg("stack: m_tile must be 32 or 64");
+        hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail("k_stack launch", e);
     }
     if (a.tp > 1) {
         static OncePerDevice once_tp;
@@ -3370,7 +3422,7 @@ struct StageTimer {          // optional hipEvent after every launch
 static int g_seq_skew = -1, g_seq_dbg_step = 0;
 
 static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, StageTimer* tm, int n_steps = 1, int tm_stride = 0,
-                     int tc_stride = 0) {
+                     int tc_stride = 0, const syn_edit* ed = nullptr) {
     if (!md || !st) return fail_msg("syn_denoise_step: null model/step");
     const int B = st->n_clips, V = st->n_variants;
     if (B <= 0 || V <= 0) return fail_msg("syn_denoise_step: n_clips and n_variants must be positive");
@@ -3384,6 +3436,11 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
     int rc;
     GArgs a;
     auto mark = [&](int c) { if (tm) tm->mark(c); };
+
+    // in-painting: the four token-major output stages blend it in (syn_denoise_step_edit has refused the wave-per-sequence kernel, which has
+    // no such operand)
+    const unsigned char* const keep = ed ? ed->keep : nullptr;
+    const float* const known = ed ? ed->known : nullptr;
 
     if (st->x_fragment_order || (st->reserved & 7) == 5) {
         // large single-variant batches: one wave per sequence, weights streamed once per 128 rows (syn_seq.inc)
@@ -3454,6 +3511,7 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
         la.xb = (const __bf16*)st->x_t_bf16; la.xt = st->x_t; la.noise = st->noise;
         la.rng = (const unsigned long long*)st->rng; la.coef = st->coef; la.t_coef = st->t_coef;
         la.xn = st->x_next; la.xnb = (__bf16*)st->x_next_bf16; la.x0 = st->pred_x0;
+        la.keep = keep; la.known = known;
         la.H = st->ws_h; la.Q = (__bf16*)st->ws_q; la.Kb = (__bf16*)st->ws_k; la.Vt = (__bf16*)st->ws_vt;
         la.HID = (__bf16*)st->ws_hid; la.sync = st->ws_sync; la.dbg = g_dbg_mlp;
         la.X0v = by_seq ? st->ws_x0v : nullptr;
@@ -3464,6 +3522,7 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
             u.X0v = st->ws_x0v; u.w = st->cfg_w; u.w_stride = st->cfg_w_clip_stride; u.V = V; u.B = B; u.Xt = st->x_t; u.noise = st->noise;
             u.rng = (const unsigned long long*)st->rng; u.coef = st->coef; u.t_coef = st->t_coef;
             u.Xn = st->x_next; u.Xnb = (__bf16*)st->x_next_bf16; u.X0 = st->pred_x0;
+            u.keep = keep; u.known = known;
             const size_t n4 = (size_t)B * SYN_T * SYN_C / 4;
             hipLaunchKernelGGL(k_guided_update, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, u);
             mark(ST_OUT);
@@ -3488,6 +3547,7 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
     aout.ldx = SYN_D; aout.x_rows = Mb; aout.W = (const uint4*)md->w_out; aout.K = SYN_D; aout.M = Mb; aout.bias = md->b_out;
     aout.Xt = st->x_t; aout.noise = st->noise; aout.rng = (const unsigned long long*)st->rng; aout.coef = st->coef;
     aout.t_coef = st->t_coef; aout.Xn = st->x_next; aout.Xnb = (__bf16*)st->x_next_bf16; aout.X0 = st->pred_x0;
+    aout.keep = keep; aout.known = known;
     const bool fuse_out = mode == 0 && V == 1;
 
     // layer implementation: 0 = whole stack in one kernel (production); 1 = five kernels per block, kept as the plain restatement the whole-stack kernel is
@@ -3560,6 +3620,18 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
 
 int syn_denoise_step(const syn_model* md, const syn_step* st, void* stream) {
     return step_impl(md, st, (hipStream_t)stream, nullptr);
+}
+
+int syn_denoise_step_edit(const syn_model* md, const syn_step* st, const syn_edit* ed, void* stream) {
+    if (ed && st) {
+        if (!ed->keep != !ed->known)
+            return fail_msg("syn_denoise_step_edit: syn_edit.keep and syn_edit.known go together (exactly one of them is NULL)");
+        if (ed->keep && st->x_fragment_order)
+            return fail_msg("syn_denoise_step_edit: x_fragment_order = 1: an edit needs the latent, keep and known token-major (the wave-per-sequence kernel takes no edit)");
+        if (ed->keep && (st->reserved & 7) == 5)
+            return fail_msg("syn_denoise_step_edit: reserved = 5 pins the wave-per-sequence kernel, which takes no edit");
+    }
+    return step_impl(md, st, (hipStream_t)stream, nullptr, 1, 0, 0, ed);
 }
 
 void syn_debug_conv_terms(int mask) { g_conv_terms = mask < 0 ? -1 : (mask & 3); }   /* diagnostics: cross products of the split-operand training convolutions (3 = all) */

@@ -50,6 +50,7 @@ struct LArgs {
     const __bf16* xb; const float* xt; const float* noise; const unsigned long long* rng;
     const float* coef; const int* t_coef;
     float* xn; __bf16* xnb; float* x0;
+    const unsigned char* keep; const float* known;      // in-painting (syn_denoise_step_edit): x0 = keep ? known : x0, or both NULL
     float* H; __bf16* Q; __bf16* Kb; __bf16* Vt; __bf16* HID;
     float* X0v;                        // != nullptr: per-sequence groups; the output stage writes x0_hat of every variant here
                                        // ([V*B*32][1536] fp32) and k_guided_update combines them and applies the step
@@ -757,6 +758,7 @@ __global__ __launch_bounds__(kThreads) void k_lat(const LArgs a) {
         const int* const t_coef = a.t_coef; const float* const coef = a.coef; const float* const b_out = a.b_out;
         const float* const xt_p = a.xt; const float* const noise = a.noise; const unsigned long long* const rng = a.rng;
         float* const xn_p = a.xn; __bf16* const xnb = a.xnb; float* const x0_p = a.x0;
+        const unsigned char* const keep = a.keep; const float* const known = a.known;
         for (int cl0 = 0; cl0 < G.nc; cl0 += 2) {
             const int ncl = min(2, G.nc - cl0);
             for (int blk = 0; blk < (a.V > 1 ? 3 : 1); ++blk) {
@@ -774,7 +776,8 @@ __global__ __launch_bounds__(kThreads) void k_lat(const LArgs a) {
                     const int tc = t_coef[clip];
                     const f32x4 cf = *reinterpret_cast<const f32x4*>(coef + (size_t)tc * 4);
                     const size_t off = (size_t)m * SYN_C + n;
-                    const f32x4 x0 = acc + pv.a;
+                    f32x4 x0 = acc + pv.a;
+                    if (keep) x0 = edit_x0(keep, known, off, x0);
                     f32x4 xn = x0 * cf[0] + pv.b * cf[1];
                     if (noise) xn = xn + *reinterpret_cast<const f32x4*>(noise + off) * cf[2];
                     else if (rng) xn = xn + randn4(rng[0], (uint64_t)tc, (rng[1] * (uint64_t)(SYN_T * SYN_C) + off) >> 2) * cf[2];

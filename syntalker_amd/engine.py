@@ -147,12 +147,15 @@ class PackedModel:
 class StepBuffers:
     """State + workspace for B clips x V conditioning variants; owns the syn_step struct."""
 
-    def __init__(self, B: int, V: int, device, want_x0: bool = False, m_tile: int = 0, layer_mode: int = 0):
+    def __init__(self, B: int, V: int, device, want_x0: bool = False, m_tile: int = 0, layer_mode: int = 0, edit: bool = False):
+        """``edit``: the buffers carry an in-painting mask and motion (`load_edit`) and every step blends them in
+        (`syn_denoise_step_edit`)."""
         self.B, self.V = B, V
         # latent layout: fragment order when the wave-per-sequence kernel runs the steps (the library's choice for large
-        # single-variant batches, or pinned with layer_mode 5), token-major otherwise
+        # single-variant batches, or pinned with layer_mode 5), token-major otherwise - and always with an edit, which that kernel
+        # does not take
         lib = _lib.load()
-        self.fragment = bool(layer_mode == 5 or (layer_mode == 0 and m_tile == 0 and lib.syn_prefers_fragment_order(B, V)))
+        self.fragment = bool(not edit and (layer_mode == 5 or (layer_mode == 0 and m_tile == 0 and lib.syn_prefers_fragment_order(B, V))))
         R, Mb = V * B * T, B * T
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)
         bf = torch.bfloat16
@@ -191,6 +194,14 @@ class StepBuffers:
         s.x_fragment_order = int(self.fragment)
         s.cfg_w_clip_stride = 3 * V if V > 1 else 0
         self.c = s
+        # in-painting: keep (nonzero = take `known` for x0) and known, token-major like x; captured graphs hold these pointers,
+        # so a later loop refills them (`load_edit`)
+        self.keep = torch.zeros(Mb, CH, dtype=torch.uint8, device=device) if edit else None
+        self.known = torch.zeros(Mb, CH, dtype=torch.float32, device=device) if edit else None
+        self.edit = None
+        if edit:
+            self.edit = _lib.SynEdit()
+            self.edit.keep, self.edit.known = self.keep.data_ptr(), self.known.data_ptr()
 
     # layout ------------------------------------------------------------------------------------
     def _import(self, src: torch.Tensor, dst_f32, dst_bf16):
@@ -204,6 +215,19 @@ class StepBuffers:
 
     def load_noise(self, eps_bct: torch.Tensor):
         self._import(eps_bct.detach().float().contiguous(), self.noise, None)
+
+    def load_edit(self, mask_bct: torch.Tensor, motion_bct: torch.Tensor):
+        """(B,1536,1,32) bool mask and float motion of an in-painting call -> keep / known (buffers built with edit=True)."""
+        if self.edit is None:
+            raise ValueError("these StepBuffers carry no edit (edit=True)")
+        shape = (self.B, CH, 1, T)
+        if tuple(mask_bct.shape) != shape or tuple(motion_bct.shape) != shape or mask_bct.dtype is not torch.bool:
+            raise ValueError(f"load_edit takes a bool mask and a motion of shape {shape}")
+        dev = self.known.device
+        motion = motion_bct.detach().to(dev, torch.float32).contiguous()
+        _lib.check(_lib.load().syn_to_token_major(motion.data_ptr(), self.B, self.known.data_ptr(), None, _lib.current_stream(dev)),
+                   "syn_to_token_major")
+        self.keep.view(self.B, T, CH).copy_(mask_bct.detach().to(dev)[:, :, 0, :].permute(0, 2, 1))
 
     def set_rng(self, seed: int, first_clip: int = 0):
         """Key of the in-epilogue generator for the whole loop; the per-step stream id is the clip's t_coef."""
@@ -244,8 +268,24 @@ def run_step(pm: PackedModel, sb: StepBuffers, coef: torch.Tensor, use_noise: bo
     if steps > 1:        # sb.c.t_model / t_coef point at [steps][n] rows (syn_steps_advance fills them)
         if use_noise and not fused_rng:
             raise ValueError("injected noise is per step: multi-step launches draw theirs (fused_rng) or run without")
+        if sb.edit is not None:
+            # `syn_denoise_steps` takes no edit: its token-major form here, one `syn_denoise_step_edit` per row of the [steps][n] int32
+            # timestep tables (row stride = 4 bytes x the vector's length, the strides `syn_denoise_steps` is given in elements)
+            tm, tc = sb.c.t_model, sb.c.t_coef
+            try:
+                for j in range(steps):
+                    sb.c.t_model, sb.c.t_coef = tm + 4 * j * sb.t_model.numel(), tc + 4 * j * sb.t_coef.numel()
+                    _lib.check(_lib.load().syn_denoise_step_edit(C.byref(pm.c), C.byref(sb.c), C.byref(sb.edit),
+                                                                 _lib.current_stream(pm.device)), "syn_denoise_step_edit")
+            finally:
+                sb.c.t_model, sb.c.t_coef = tm, tc
+            return
         _lib.check(_lib.load().syn_denoise_steps(C.byref(pm.c), C.byref(sb.c), steps, sb.t_model.numel(), sb.t_coef.numel(),
                                                  _lib.current_stream(pm.device)), "syn_denoise_steps")
+        return
+    if sb.edit is not None:
+        _lib.check(_lib.load().syn_denoise_step_edit(C.byref(pm.c), C.byref(sb.c), C.byref(sb.edit), _lib.current_stream(pm.device)),
+                   "syn_denoise_step_edit")
         return
     _lib.check(_lib.load().syn_denoise_step(C.byref(pm.c), C.byref(sb.c), _lib.current_stream(pm.device)), "syn_denoise_step")
 

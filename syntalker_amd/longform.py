@@ -46,20 +46,64 @@ def window_inputs(i: int, audio, word, seed_latent, last_sample, round_l: int, p
     return y
 
 
+PARTS = ("upper", "hands", "lower")    # the latent's channel thirds (trainer lines 458-470, `decode_take`)
+
+
+def keep_mask(n_latent: int, parts=("lower",), frames=None) -> torch.Tensor:
+    """Bool (n_latent, 1536) mask for `sample_long(edit=...)`: True where the known take is kept.  It is the union of the channel
+    thirds named in `parts` ("upper" / "hands" / "lower") over all frames and of all channels over the latent-frame ranges `frames` -
+    one half-open (a, b) or a list of them.  keep_mask(n, ("lower",)) keeps the lower body; keep_mask(n, (), [(0, 10), (20, n)]) keeps
+    everything but frames 10..19."""
+    m = torch.zeros(n_latent, 1536, dtype=torch.bool)
+    for name in parts:
+        if name not in PARTS:
+            raise ValueError(f"unknown body part {name!r}: one of {PARTS}")
+        k = PARTS.index(name)
+        m[:, 512 * k:512 * (k + 1)] = True
+    if frames is not None:
+        ranges = [frames] if len(frames) == 2 and all(isinstance(v, int) for v in frames) else list(frames)
+        for a, b in ranges:
+            if not 0 <= a <= b <= n_latent:
+                raise ValueError(f"frame range ({a}, {b}) outside 0..{n_latent}")
+            m[a:b] = True
+    return m
+
+
+def window_edit(i: int, known_latent, keep, round_l: int, window: int = 32, squeeze: int = 4):
+    """(inpainted_motion, inpainting_mask) of window i, each (B, 1536, 1, window): latent frames i * round_l / squeeze ... + window - 1 of
+    the take's `known_latent` (B, n / squeeze, 1536) and of `keep` (bool, broadcastable to it)."""
+    lo = i * round_l // squeeze
+    if known_latent.shape[1] < lo + window:
+        raise ValueError(f"window {i} covers latent frames {lo}..{lo + window - 1}; known_latent has {known_latent.shape[1]}")
+    cut = lambda t: t[:, lo:lo + window].permute(0, 2, 1).unsqueeze(2).contiguous()
+    return cut(known_latent), cut(keep.expand(known_latent.shape))
+
+
 def sample_long(diffusion, model, audio, word, seed_latent, n_pose: int | None = None, *, pose_length: int = 128,
                 pre_frames: int = 4, squeeze: int = 4, use_ddim: bool = False, style_dim: int = 512, noise_fn=None,
-                step_noise_fn=None, seed: int | None = None, skip_timesteps: int = 0, progress: bool = False, y_extra: dict | None = None):
+                step_noise_fn=None, seed: int | None = None, skip_timesteps: int = 0, progress: bool = False, y_extra: dict | None = None,
+                edit=None):
     """Returns latents (B, rounds*round_l/squeeze + pre_frames, 1536): window 0 whole, later windows without their
     first pre_frames rows (trainer lines 468-476).
     noise_fn(i) -> x_T of window i or None (library draws it); step_noise_fn(i) -> injected per-step noise or None;
-    seed: base key of the library's counter-based generator (window i uses seed + i)."""
+    seed: base key of the library's counter-based generator (window i uses seed + i).
+    edit = (known_latent, keep): in-painting over the whole take - known_latent (B, n/squeeze, 1536) in the sampler's latent space
+    (`poses.encode_take`'s latent_in), keep a bool tensor broadcastable to it (`keep_mask`); every window gets its slices as
+    y['inpainted_motion'] / y['inpainting_mask'], so the kept entries of the result are known_latent's."""
     n_pose = word.shape[1] if n_pose is None else n_pose
     round_l, rounds, _ = window_plan(n_pose, pose_length, pre_frames, squeeze)
     bs = word.shape[0]
     loop = diffusion.ddim_sample_loop if use_ddim else diffusion.p_sample_loop
+    if edit is not None:
+        known_latent, keep = edit
+        if keep.dtype is not torch.bool:
+            raise ValueError("edit: keep is a bool tensor (longform.keep_mask)")
+        keep = keep.to(known_latent.device)
     pieces, last = [], None
     for i in range(rounds):
         y = window_inputs(i, audio, word, seed_latent, last, round_l, pre_frames, squeeze, style_dim, y_extra)
+        if edit is not None:
+            y["inpainted_motion"], y["inpainting_mask"] = window_edit(i, known_latent, keep, round_l, pose_length // squeeze, squeeze)
         kw = {}
         if step_noise_fn is not None:
             kw["step_noise"] = step_noise_fn(i)

@@ -302,9 +302,24 @@ class GaussianDiffusion:
                 or const_noise or randomize_class or cond_fn_with_grad:
             return None, None
         y = (model_kwargs or {}).get("y")
-        if y is None or "inpainting_mask" in y or tuple(shape[1:]) != (engine.CH, 1, engine.T):
+        if y is None or tuple(shape[1:]) != (engine.CH, 1, engine.T):
+            return None, None
+        if "inpainting_mask" in y and not self._edit_operands_ok(y, shape):
             return None, None
         return mdm, plan_fn
+
+    @staticmethod
+    def _edit_operands_ok(y, shape):
+        """The in-painting call the fused loop takes: a bool `inpainting_mask` and a float `inpainted_motion`, each of the loop's
+        shape.  Anything else - a mask without a motion (which the reference ignores), a non-bool mask - is the generic path's."""
+        m, k = y["inpainting_mask"], y.get("inpainted_motion")
+        return (torch.is_tensor(m) and torch.is_tensor(k) and m.dtype is torch.bool and k.is_floating_point()
+                and tuple(m.shape) == tuple(shape) and tuple(k.shape) == tuple(shape))
+
+    @property
+    def last_path(self):
+        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` call took (None before the first)."""
+        return getattr(self, "_last_path", None)
 
     def _fused(self, kind, mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image, step_noise,
                seed, progress, each=None, first_clip=0):
@@ -315,7 +330,7 @@ class GaussianDiffusion:
         dev = next(mdm.parameters()).device
         B = shape[0]
         slices = [(0, B)]
-        if each is None and not progress:
+        if each is None and not progress and "inpainting_mask" not in model_kwargs["y"]:    # (an edit runs as one token-major slice)
             with torch.no_grad():
                 slices = engine.plan_slices(B, len(plan_fn(model_kwargs["y"]).variants), dev)
         if len(slices) == 1:
@@ -349,7 +364,10 @@ class GaussianDiffusion:
         with torch.no_grad():
             plan = plan_fn(y)
             V = len(plan.variants)
-            pm, sb = mdm.packed(), mdm.step_buffers(B, V, want_x0=each is not None)
+            edit = "inpainting_mask" in y                                   # (`_fusable` has checked the pair)
+            pm, sb = mdm.packed(), mdm.step_buffers(B, V, want_x0=each is not None, edit=edit)
+            if edit:
+                sb.load_edit(y["inpainting_mask"], y["inpainted_motion"])
             sb.cond.copy_((mdm.variant_conds(y, plan.variants) if conds is None else conds).reshape(-1, engine.D))
             if V > 1:
                 sb.cfg_w.copy_(plan.tensor(dev))
@@ -438,6 +456,7 @@ class GaussianDiffusion:
         (keys the counter-based noise so results do not depend on the sharding)."""
         mdm, plan_fn = self._fusable(model, model_kwargs, denoised_fn, cond_fn, clip_denoised, const_noise,
                                      randomize_class, cond_fn_with_grad, shape)
+        self._last_path = "generic" if mdm is None else "fused"
         if mdm is not None:
             dump = []
             each = None
@@ -473,6 +492,7 @@ class GaussianDiffusion:
             raise NotImplementedError()          # same as the reference (:912-915)
         mdm, plan_fn = self._fusable(model, model_kwargs, denoised_fn, cond_fn, clip_denoised, False,
                                      randomize_class, cond_fn_with_grad, shape)
+        self._last_path = "generic" if mdm is None else "fused"
         if mdm is not None:
             return self._fused("ddim", mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image,
                                step_noise, seed, progress, None, first_clip)
