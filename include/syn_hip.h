@@ -87,8 +87,10 @@ typedef struct syn_step {
     int32_t n_clips;        /* B                                                                 */
     int32_t n_variants;     /* V >= 1                                                            */
     int32_t m_tile;         /* rows per workgroup: 0 = auto, else 32 / 64 / 128                  */
-    int32_t reserved;       /* kernel selection: 0 = auto (small-batch kernel up to 8 sequences when ws_sync != NULL, the whole-step
-                               kernel with split tiles at 9..128 sequences when ws_xch != NULL, else the whole-step kernel); 4 = whole-step kernel always;
+    int32_t reserved;       /* kernel selection: 0 = auto, one rule (plan_step in csrc/syn_step_plan.inc): the small-batch kernel while an XCD holds at most
+                               4 sequences (ws_sync != NULL; sequences are dealt to the 8 XCDs when V == 1 or ws_x0v != NULL - up to 32 of them - else
+                               whole clips with their V variants), unless the whole-step kernel's split tiles apply (9..128 sequences, ws_sync and
+                               ws_xch != NULL); else the whole-step kernel on whole tiles; 4 = whole-step kernel always;
                                3 = small-batch kernel always; 1 = five kernels per block (the plain restatement the whole-step kernel is checked against bit for bit);
                                5 = wave-per-sequence kernel always (needs x_fragment_order = 1);
                                +8 = never split a tile over several workgroups (see ws_xch)               */

@@ -11,7 +11,6 @@ using tmr::kArow;
 using tmr::kBM;
 using tmr::kBN;
 using tmr::kKC;
-using tmr::launched;
 using tmr::load8;
 using tmr::split8;
 

@@ -28,7 +28,7 @@
 // Files: this one holds the token-resident whole-step kernel k_stack (large batches), the A/B kernels, the small
 // kernels and every C-ABI entry point; syn_latency.inc the persistent small-batch kernel k_lat; syn_wavenc.inc the
 // WavEncoder convolutions (per-clip conditioning); syn_train.inc the fp32 forward / backward kernels of the
-// training path.
+// training path; syn_step_plan.inc (plain C++, no HIP) the choice of the kernel that runs a step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1609,9 +1609,16 @@ int fail_msg(const char* what) {
     snprintf(g_err, sizeof(g_err), "%s", what);
     return -2;
 }
+int launched(const char* what) {     // after a launch: 0, or the launch's error under the label `what`
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(what, e);
+}
 
 static int g_gemm_resident = 2;      // 16-row plain GEMMs: 2 = 16 x 128 tiles, activation block resident in the LDS, deep weight ring; 1 = the same loop on
                                      // 16 x 512 tiles; 0 = the streaming loop (syn_debug_gemm_resident: A/B)
+
+#include "syn_step_plan.inc"
+static_assert(kPlanT == SYN_T && kPlanXcds == lat::kGroups, "the step planner restates the sequence length and the XCD count");
 
 int device_cus();
 constexpr int kN128Lds = 128 * 1024;
@@ -1649,8 +1656,7 @@ int launch_gemm(const GArgs& a, int mt, int chunks, hipStream_t s) {
             return fail_msg("gemm: 16-row tiles exist for the plain epilogue only");
         default:  return fail_msg("gemm: m_tile must be 16, 32, 64 or 128");
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_gemm launch", e);
+    return launched("k_gemm launch");
 }
 
 template <typename K>
@@ -1682,51 +1688,41 @@ void n128_setup() {
     }
 }
 
+// The nine k_stack instances: whole tiles of 64 / 32 rows, 32-row tiles split over 2 / 4 workgroups and 64-row tiles over 2; the in-painting
+// (EDIT) form of the whole tiles and of the split 32-row ones.  Each raises its LDS limit on first use, per device.
+struct StackInstance {
+    int rows, tp;                    // tp: 0 = whole tiles
+    bool edit;
+    void (*kernel)(SArgs);
+    OncePerDevice once;
+    int lds() const { return rows * 2048 + 4096; }
+};
+StackInstance* stack_instance(int rows, int tp, bool edit) {
+    static StackInstance table[] = {
+        {64, 0, false, k_stack<64>},          {32, 0, false, k_stack<32>},
+        {64, 0, true,  k_stack<64, 0, true>}, {32, 0, true,  k_stack<32, 0, true>}, {32, 2, true, k_stack<32, 2, true>}, {32, 4, true, k_stack<32, 4, true>},
+        {32, 2, false, k_stack<32, 2>},       {32, 4, false, k_stack<32, 4>},       {64, 2, false, k_stack<64, 2>},
+    };
+    for (StackInstance& i : table)
+        if (i.rows == rows && i.tp == tp && i.edit == edit) return &i;
+    return nullptr;
+}
+
 int launch_stack(const SArgs& a, int mt, hipStream_t s) {
-    static OncePerDevice once;
-    if (once.first()) {
-        allow_lds(k_stack<64>, 64 * 2048 + 4096);
-        allow_lds(k_stack<32>, 32 * 2048 + 4096);
-    }
+    const bool edit = a.out.keep != nullptr;           // in-painting
     dim3 grid((a.M + mt - 1) / mt), block(kThreads);
     if (a.tp > 1) {
         if (!(mt == 32 || (mt == 64 && a.tp == 2)) || !a.sync || !a.xch) return fail_msg("stack: the tile-split mode needs 32-row tiles (or 64-row tiles split in two), ws_sync and ws_xch");
         grid.x = lat::kGroups * a.tp * ((a.tp_tiles + lat::kGroups - 1) / lat::kGroups);    // whole groups on every XCD
         if (grid.x > 256) return fail_msg("stack: the tensor-parallel mode needs all its workgroups resident (<= 256)");
+        if (edit && mt != 32) return fail_msg("stack: an edit takes split tiles of 32 rows only");
+        if (a.tp != 2 && a.tp != 4) return fail_msg("stack: tile split over 2 or 4 workgroups only");
     }
-    if (a.out.keep) {          // in-painting: the EDIT instances (32-row tiles whole or split, 64-row tiles whole)
-        static OncePerDevice once_ed;
-        if (once_ed.first()) {
-            allow_lds(k_stack<64, 0, true>, 64 * 2048 + 4096); allow_lds(k_stack<32, 0, true>, 32 * 2048 + 4096);
-            allow_lds(k_stack<32, 2, true>, 32 * 2048 + 4096); allow_lds(k_stack<32, 4, true>, 32 * 2048 + 4096);
-        }
-        if (a.tp > 1 && mt != 32) return fail_msg("stack: an edit takes split tiles of 32 rows only");
-        if (a.tp == 4) hipLaunchKernelGGL((k_stack<32, 4, true>), grid, block, 32 * 2048 + 4096, s, a);
-        else if (a.tp == 2) hipLaunchKernelGGL((k_stack<32, 2, true>), grid, block, 32 * 2048 + 4096, s, a);
-        else if (a.tp > 1) return fail_msg("stack: tile split over 2 or 4 workgroups only");
-        else if (mt == 64) hipLaunchKernelGGL((k_stack<64, 0, true>), grid, block, 64 * 2048 + 4096, s, a);
-        else if (mt == 32) hipLaunchKernelGGL((k_stack<32, 0, true>), grid, block, 32 * 2048 + 4096, s, a);
-        else return fail_msg("stack: m_tile must be 32 or 64");
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail("k_stack launch", e);
-    }
-    if (a.tp > 1) {
-        static OncePerDevice once_tp;
-        if (once_tp.first()) { allow_lds(k_stack<32, 2>, 32 * 2048 + 4096); allow_lds(k_stack<32, 4>, 32 * 2048 + 4096); allow_lds(k_stack<64, 2>, 64 * 2048 + 4096); }
-        if (mt == 64) hipLaunchKernelGGL((k_stack<64, 2>), grid, block, 64 * 2048 + 4096, s, a);
-        else if (a.tp == 4) hipLaunchKernelGGL((k_stack<32, 4>), grid, block, 32 * 2048 + 4096, s, a);
-        else if (a.tp == 2) hipLaunchKernelGGL((k_stack<32, 2>), grid, block, 32 * 2048 + 4096, s, a);
-        else return fail_msg("stack: tile split over 2 or 4 workgroups only");
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail("k_stack launch", e);
-    }
-    switch (mt) {
-        case 64: hipLaunchKernelGGL(k_stack<64>, grid, block, 64 * 2048 + 4096, s, a); break;
-        case 32: hipLaunchKernelGGL(k_stack<32>, grid, block, 32 * 2048 + 4096, s, a); break;
-        default: return fail_msg("stack: m_tile must be 32 or 64");
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_stack launch", e);
+    StackInstance* const k = stack_instance(mt, a.tp > 1 ? a.tp : 0, edit);
+    if (!k) return fail_msg("stack: m_tile must be 32 or 64");
+    if (k->once.first()) allow_lds(k->kernel, k->lds());
+    hipLaunchKernelGGL(k->kernel, grid, block, k->lds(), s, a);
+    return launched("k_stack launch");
 }
 
 #include "syn_stack_train.inc"
@@ -1773,8 +1769,7 @@ int launch_conv(const wav::CArgs& a, int n_clips, hipStream_t s) {
     static OncePerDevice once;
     if (once.first()) { allow_lds(wav::k_conv<CINP, KT, WN, WM, RF, EPI>, lds); }
     hipLaunchKernelGGL((wav::k_conv<CINP, KT, WN, WM, RF, EPI>), dim3((a.L_out + MW - 1) / MW, n_clips), dim3(WN * WM * 64), lds, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv launch", e);
+    return launched("k_conv launch");
 }
 
 // diagnostics (syn_debug_conv_terms): which of the two cross products of the split-operand convolutions are issued (3 = both)
@@ -1793,8 +1788,7 @@ int launch_conv_train_ks(const wav::TArgs& a0, int n_clips, hipStream_t s) {
     static OncePerDevice once;
     if (once.first()) { allow_lds(wav::k_conv_train_ks<CINP, KT, RF>, lds); }
     hipLaunchKernelGGL((wav::k_conv_train_ks<CINP, KT, RF>), dim3((a.L_out + MW - 1) / MW, n_clips), dim3(256), lds, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_train_ks launch", e);
+    return launched("k_conv_train_ks launch");
 }
 
 // n_out: output channels this launch covers (a multiple of the instance's WN x NF x 16 channels per workgroup: grid z)
@@ -1807,8 +1801,7 @@ int launch_conv_train(const wav::TArgs& a0, int n_clips, hipStream_t s, int n_ou
     static OncePerDevice once;
     if (once.first()) { allow_lds(wav::k_conv_train<CINP, KT, WN, WM, RF, NF, DUAL>, lds); }
     hipLaunchKernelGGL((wav::k_conv_train<CINP, KT, WN, WM, RF, NF, DUAL>), dim3((a.L_out + MW - 1) / MW, n_clips, n_out / NT), dim3(WN * WM * 64), lds, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_train launch", e);
+    return launched("k_conv_train launch");
 }
 
 template <int CO_T, int TAPS, bool DUAL = false>
@@ -1818,8 +1811,7 @@ int launch_wgrad_s(const wav::WArgs& a0, hipStream_t s) {
     static OncePerDevice once;
     if (once.first()) { allow_lds(wav::k_conv_wgrad_s<CO_T, TAPS, DUAL>, wav::wgrad_s_lds(CO_T)); }
     hipLaunchKernelGGL((wav::k_conv_wgrad_s<CO_T, TAPS, DUAL>), dim3(a.cin / wav::kWsJ, a.shares, DUAL ? 1 : a.co_n / CO_T), dim3(512), wav::wgrad_s_lds(CO_T), s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_wgrad_s launch", e);
+    return launched("k_conv_wgrad_s launch");
 }
 
 // The 128- / 256-channel stride-1 layers on 64-channel output tiles (grid z) with 32 input channels per workgroup: the gradient is cut in cout / 64 x cin / 32 slices
@@ -1836,8 +1828,7 @@ int launch_wgrad_tiled(const wav::WArgs& a0, hipStream_t s) {
     static OncePerDevice once;
     if (once.first()) { allow_lds(wav::k_conv_wgrad<CO_T, TAPS, CB>, wav::wgrad_lds2(CO_T, CB)); }
     hipLaunchKernelGGL((wav::k_conv_wgrad<CO_T, TAPS, CB>), dim3(a.cin / (16 * CB), a.shares, a.co_n / CO_T), dim3(512), wav::wgrad_lds2(CO_T, CB), s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_wgrad (tiled) launch", e);
+    return launched("k_conv_wgrad (tiled) launch");
 }
 
 template <int CO, int TAPS>
@@ -1847,22 +1838,14 @@ int launch_wgrad(const wav::WArgs& a0, hipStream_t s) {
     constexpr int CB = wav::wgrad_cb(CO);
     if (once.first()) { allow_lds(wav::k_conv_wgrad<CO, TAPS, CB>, wav::wgrad_lds(CO)); }
     hipLaunchKernelGGL((wav::k_conv_wgrad<CO, TAPS, CB>), dim3(a.cin / (16 * CB), a.shares), dim3(512), wav::wgrad_lds(CO), s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_wgrad launch", e);
+    return launched("k_conv_wgrad launch");
 }
 
 int launch_latency(const lat::LArgs& a, hipStream_t s) {
     static OncePerDevice once;
     if (once.first()) { allow_lds(lat::k_lat, lat::kLds); }
     hipLaunchKernelGGL(lat::k_lat, dim3(lat::kGroups * lat::kP), dim3(kThreads), lat::kLds, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_lat launch", e);
-}
-
-// workgroups of a k_seq launch: 4 sequences each; a guided clip's V variants never straddle a workgroup
-int seq_grid(int n_clips, int n_variants) {
-    const int cpw = n_variants == 1 ? 4 : 4 / n_variants;
-    return (n_clips + cpw - 1) / cpw;
+    return launched("k_lat launch");
 }
 
 template <bool G, int NZ>
@@ -1880,8 +1863,7 @@ int launch_seq(const seq::QArgs& a, hipStream_t s) {
     } else {
         if (nz == 2) launch_seq_as<true, 2>(a, grid, s); else if (nz == 1) launch_seq_as<true, 1>(a, grid, s); else launch_seq_as<true, 0>(a, grid, s);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_seq launch", e);
+    return launched("k_seq launch");
 }
 
 int device_cus() {
@@ -1907,16 +1889,6 @@ bool latency_path_ok() {
     return ok == 1;
 }
 
-int pick_tile(int rows) {
-    // enough workgroups to cover the 256 CUs first, then the larger tile (weight reuse per L2 byte).
-    // 128-row tiles exist for the A/B paths only: with the 4-slot weight ring they exceed 256 VGPRs.
-    if (rows / 64 >= 192) return 64;
-    // more 32-row tiles than CUs would mean a second, mostly empty round of workgroups (257..383 sequences: 0.84 ms per step against
-    // 0.52 ms on 64-row tiles, `profiles/r02_diag_batch_sweep.txt`); up to one tile per CU the smaller tile wins (0.41-0.46 against 0.52 ms)
-    if ((rows + 31) / 32 > device_cus()) return 64;
-    return 32;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1932,8 +1904,7 @@ int syn_pack_weight(const float* w, int32_t n, int32_t k, void* out_packed, void
     if (!w || !out_packed || n % 16 || k % 32) return fail_msg("syn_pack_weight: need n%16==0, k%32==0, non-null pointers");
     const int total = (n / 16) * (k / 32) * 64;
     hipLaunchKernelGGL(k_pack, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, n, k, (uint4*)out_packed);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_pack launch", e);
+    return launched("k_pack launch");
 }
 
 int syn_pack_weights(const syn_pack_job* jobs_dev, int32_t n_jobs, int64_t max_fragments, void* stream) {
@@ -1941,8 +1912,7 @@ int syn_pack_weights(const syn_pack_job* jobs_dev, int32_t n_jobs, int64_t max_f
     if (!jobs_dev || n_jobs <= 0 || max_fragments <= 0) return fail_msg("syn_pack_weights: bad arguments");
     hipLaunchKernelGGL(k_pack_many, dim3((unsigned)((max_fragments * 64 + 255) / 256), n_jobs), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const PackJob*>(jobs_dev));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_pack_many launch", e);
+    return launched("k_pack_many launch");
 }
 
 int syn_pack_weight_t(const void* s_kn, int32_t is_bf16, int32_t n, int32_t k, void* out_packed, void* stream) {
@@ -1954,53 +1924,34 @@ int syn_pack_weight_t(const void* s_kn, int32_t is_bf16, int32_t n, int32_t k, v
     else
         hipLaunchKernelGGL(k_pack_t<float>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)s_kn, n, k,
                            (uint4*)out_packed);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_pack_t launch", e);
+    return launched("k_pack_t launch");
 }
 
 int syn_to_token_major(const float* x_bct, int32_t n_clips, float* out_f32, void* out_bf16, void* stream) {
     if (!x_bct || n_clips <= 0) return fail_msg("syn_to_token_major: bad arguments");
     hipLaunchKernelGGL(k_to_token_major, dim3(n_clips, SYN_C / 64), dim3(256), 0, (hipStream_t)stream, x_bct, out_f32,
                        (__bf16*)out_bf16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_to_token_major launch", e);
+    return launched("k_to_token_major launch");
 }
 
-int32_t syn_prefers_fragment_order(int32_t n_clips, int32_t n_variants) {
-    // k_seq runs 4 sequences per CU and pass, k_stack 2; measured per pass at full occupancy (profiles/r02_diag_seq.txt):
-    // 1.26 ms against 0.66 ms.  Both quantise to whole passes over the 256 CUs, so the choice follows the pass counts:
-    // 1024 / 2048 / 3072 clips -> k_seq, 1280 or 1536 -> k_stack (a second, mostly empty k_seq pass would cost more).
-    // Guided batches: the V variants of a clip are the waves of one workgroup (2 clips per workgroup at V = 2, one at V = 3
-    // - a wave idles - and 4); k_stack sees V * n_clips sequences.
-    if (n_variants < 1 || n_variants > 4) return 0;
-    const int cus = device_cus();
-    const long wgs = seq_grid(n_clips, n_variants), seqs = (long)n_clips * n_variants;
-    // (no minimum fill: from 513 sequences on k_stack needs a second, mostly empty round - 1.10 ms per step whatever the size - where
-    // k_seq's single pass of 129..192 workgroups takes 0.88-0.92 ms: 612 k against 492 k clip-steps/s at 544 clips, 763 k against 630 k at 704)
-    const long passes_seq = (wgs + cus - 1) / cus, passes_stack = (seqs + 2L * cus - 1) / (2L * cus);
-    // (V = 3 leaves a wave of every workgroup idle: measured 1197 us against k_stack's 1120 at 256 clips)
-    return passes_seq * (n_variants == 3 ? 255 : 191) < passes_stack * 100 ? 1 : 0;
-}
+int32_t syn_prefers_fragment_order(int32_t n_clips, int32_t n_variants) { return prefers_fragment_order(n_clips, n_variants, device_cus()); }
 
 int syn_x_to_fragment(const float* x_bct, int32_t n_clips, float* out_f32, void* out_bf16, void* stream) {
     if (!x_bct || n_clips <= 0) return fail_msg("syn_x_to_fragment: bad arguments");
     hipLaunchKernelGGL(seq::k_x_to_fragment, dim3(n_clips, SYN_C / 32), dim3(256), 0, (hipStream_t)stream, x_bct, out_f32, (uint4*)out_bf16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_x_to_fragment launch", e);
+    return launched("k_x_to_fragment launch");
 }
 
 int syn_x_from_fragment(const float* x_frag, int32_t n_clips, float* out_bct, void* stream) {
     if (!x_frag || !out_bct || n_clips <= 0) return fail_msg("syn_x_from_fragment: bad arguments");
     hipLaunchKernelGGL(seq::k_x_from_fragment, dim3(n_clips, SYN_C / 32), dim3(256), 0, (hipStream_t)stream, x_frag, out_bct);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_x_from_fragment launch", e);
+    return launched("k_x_from_fragment launch");
 }
 
 int syn_from_token_major(const float* x_btc, int32_t n_clips, float* out_bct, void* stream) {
     if (!x_btc || !out_bct || n_clips <= 0) return fail_msg("syn_from_token_major: bad arguments");
     hipLaunchKernelGGL(k_from_token_major, dim3(n_clips, SYN_C / 64), dim3(256), 0, (hipStream_t)stream, x_btc, out_bct);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_from_token_major launch", e);
+    return launched("k_from_token_major launch");
 }
 
 int syn_axpby_rows(const float* x, const float* y, const float* coef_ab, const int32_t* t_row, int32_t n_clips,
@@ -2009,8 +1960,7 @@ int syn_axpby_rows(const float* x, const float* y, const float* coef_ab, const i
     const long n4 = (long)n_clips * per_clip / 4;
     hipLaunchKernelGGL(k_axpby_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, coef_ab,
                        t_row, n4, per_clip / 4, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_axpby_rows launch", e);
+    return launched("k_axpby_rows launch");
 }
 
 // ---- RVQ-VAE (syn_rvq.inc) ----------------------------------------------------------------------------------------
@@ -2034,8 +1984,7 @@ int syn_vq_conv1d(const syn_vq_conv* cv, const void* x_bf16, const float* resid,
     if (once.first()) { allow_lds(rvq::k_conv1d<2>, 160 * 1024); }
     const dim3 grid((t_out + mt - 1) / mt, cv->cout / 128, clips);
     hipLaunchKernelGGL(rvq::k_conv1d<mf>, grid, dim3(rvq::kCvThreads), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv1d launch", e);
+    return launched("k_conv1d launch");
 }
 
 namespace {
@@ -2149,15 +2098,13 @@ int syn_vq_quantize(const float* x, const float* codebooks, const float* codeboo
     a.sqerr = sqerr; a.hist = hist; a.rows = rows;
     if (rvq::q_rows(rows) == 4) hipLaunchKernelGGL(rvq::k_quantize<4>, dim3(syn_vq_quantize_groups(rows)), dim3(rvq::kQThreads), 0, (hipStream_t)stream, a);
     else                        hipLaunchKernelGGL(rvq::k_quantize<16>, dim3(syn_vq_quantize_groups(rows)), dim3(rvq::kQThreads), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_quantize launch", e);
+    return launched("k_quantize launch");
 }
 
 int syn_vq_codes(const int32_t* idx, const float* codebooks, float* q_f32, void* q_bf16, int32_t rows, int32_t n_q, void* stream) {
     if (!idx || !codebooks || !q_f32 || rows <= 0 || n_q < 1 || n_q > rvq::kQ) return fail_msg("syn_vq_codes: bad arguments");
     hipLaunchKernelGGL(rvq::k_codes, dim3(rows), dim3(rvq::kDim), 0, (hipStream_t)stream, idx, codebooks, q_f32, (__bf16*)q_bf16, rows, n_q);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_codes launch", e);
+    return launched("k_codes launch");
 }
 
 int syn_steps_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, int32_t n_t_model, int32_t* t_coef, int32_t n_t_coef,
@@ -2166,8 +2113,7 @@ int syn_steps_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, 
         return fail_msg("syn_steps_advance: bad arguments");
     hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)sched, (int*)counter, (int*)t_model,
                        n_t_model, (int*)t_coef, n_t_coef, n_steps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_step_advance launch", e);
+    return launched("k_step_advance launch");
 }
 
 int syn_step_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, int32_t n_t_model, int32_t* t_coef, int32_t n_t_coef,
@@ -2180,24 +2126,21 @@ int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t 
     const long n4 = n / 4;
     hipLaunchKernelGGL(k_randn, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n4, seed,
                        stream_id, (long)(first_index / 4));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_randn launch", e);
+    return launched("k_randn launch");
 }
 
 int syn_axis_angle_to_rot6d(const float* axis_angle, int64_t n_joints, float* rot6d, void* stream) {
     if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_axis_angle_to_rot6d: null pointer / negative count");
     if (n_joints == 0) return 0;
     hipLaunchKernelGGL(pose::k_aa_to_rot6d, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, axis_angle, (long)n_joints, rot6d);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_aa_to_rot6d launch", e);
+    return launched("k_aa_to_rot6d launch");
 }
 
 int syn_rot6d_to_axis_angle(const float* rot6d, int64_t n_joints, float* axis_angle, void* stream) {
     if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_rot6d_to_axis_angle: null pointer / negative count");
     if (n_joints == 0) return 0;
     hipLaunchKernelGGL(pose::k_rot6d_to_aa, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rot6d, (long)n_joints, axis_angle);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_rot6d_to_aa launch", e);
+    return launched("k_rot6d_to_aa launch");
 }
 
 // TMR encoders (syn_tmr.inc)
@@ -2250,7 +2193,7 @@ int syn_test_gemm(const void* x_bf16, const void* w_packed, const float* bias, i
     a.bias = bias; a.Yf = y; a.ldyf = n;
     a.ablate = m_tile >> 16;              // diagnostics: upper bits of m_tile
     m_tile &= 0xffff;
-    return launch_gemm<EPI_PLAIN>(a, m_tile ? m_tile : pick_tile(m_rows), n / kNT, (hipStream_t)stream);
+    return launch_gemm<EPI_PLAIN>(a, m_tile ? m_tile : pick_tile(m_rows, device_cus()), n / kNT, (hipStream_t)stream);
 }
 
 static int g_linear_mt = 0;
@@ -2274,6 +2217,7 @@ static int linear_impl(const void* x_bf16, const void* w_packed, const float* bi
         // with 128 / 256 / 384 inputs over more than 4096 rows: text_encoder_body beyond 32 clips) goes out as slices of 4096, every slice after the
         // first adding to what the one before it stored (the residual epilogue reading the output in place) - a fixed order, run-to-run identical.
         constexpr int kSlice = kN128Lds / 32;
+        static_assert(kSlice * 32 <= kN128Lds, "a slice's activation block fits the LDS at 16-row tiles, so pick_mt128 never answers 0 for it");
         n128_setup();
         for (int k0 = 0; k0 < k; k0 += kSlice) {
             GArgs b = a;
@@ -2281,20 +2225,19 @@ static int linear_impl(const void* x_bf16, const void* w_packed, const float* bi
             b.X = a.X + k0; b.W = a.W + (size_t)(k0 / 32) * 64; b.w_ks = k / 32;
             if (k0) { b.bias = nullptr; b.res = y; }
             b.mt128 = pick_mt128(m_rows, n, b.K);
+            if (!b.mt128) return fail_msg("syn_linear: a K slice does not fit the 128-column kernel's LDS");
             hipLaunchKernelGGL(k_gemm_n128, dim3((m_rows + b.mt128 - 1) / b.mt128, n / 128), dim3(kThreads), b.mt128 * b.K * 2, (hipStream_t)stream, b);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(who, e);
+        if (int rc = launched(who)) return rc;
         return xt_packed ? syn_pack_weight_t(x_bf16, 1, k, m_rows, xt_packed, stream) : 0;
     }
     if (!xt_packed && !res && !gelu_bf16 && m_rows <= 64 && k >= 2048 && g_linear_mt == 0 && g_gemm_resident) {       // a few rows, long K: split K over the waves
         hipLaunchKernelGGL(k_gemm_skinny, dim3(n / 16, (m_rows + 15) / 16), dim3(kThreads), 0, (hipStream_t)stream, a);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail("k_gemm_skinny launch", e);
+        return launched("k_gemm_skinny launch");
     }
     if (!xt_packed || m_rows > 2048 || g_linear_mt > 0) {            // no pack, or larger row tiles: the pack is a launch of its own
         // the training step's GEMMs have 512 .. 1536 rows: 16-row tiles give 32 .. 96 x (n / 512) workgroups, twice what 32-row ones do
-        const int mt = g_linear_mt > 0 ? g_linear_mt : (m_rows <= 2048 ? 16 : pick_tile(m_rows));
+        const int mt = g_linear_mt > 0 ? g_linear_mt : (m_rows <= 2048 ? 16 : pick_tile(m_rows, device_cus()));
         if (int rc = launch_gemm<EPI_PLAIN>(a, mt, n / kNT, (hipStream_t)stream)) return rc;
         return xt_packed ? syn_pack_weight_t(x_bf16, 1, k, m_rows, xt_packed, stream) : 0;
     }
@@ -2307,8 +2250,7 @@ static int linear_impl(const void* x_bf16, const void* w_packed, const float* bi
         hipLaunchKernelGGL((k_gemm_and_pack<16, 1>), dim3((m_rows + 15) / 16, n / kNT, 2), dim3(kThreads), k * 32, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((k_gemm_and_pack<16, 0>), dim3((m_rows + 15) / 16, n / kNT, 2), dim3(kThreads), 2 * 32 * 128 + 1024, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(who, e);
+    return launched(who);
 }
 
 int syn_linear(const void* x_bf16, const void* w_packed, const float* bias, int32_t m_rows, int32_t n, int32_t k, float* y,
@@ -2347,8 +2289,7 @@ int syn_linear_pair(const void* x1_bf16, const void* w1_packed, int32_t m1, int3
         if (int rc = syn_linear(x2_bf16, w2_packed, nullptr, m2, n2, k2, y2, stream)) return rc;
         if (bias_grad) {
             hipLaunchKernelGGL(glu::k_colsum_parts, dim3((part_n + 63) / 64), dim3(64), 0, (hipStream_t)stream, bias_parts, part_rows, part_n, bias_grad);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail("k_colsum_parts launch", e);
+            if (int rc = launched("k_colsum_parts launch")) return rc;
         }
         return 0;
     }
@@ -2379,8 +2320,7 @@ int syn_linear_pair(const void* x1_bf16, const void* w1_packed, int32_t m1, int3
         hipLaunchKernelGGL((k_gemm_pair<16, 1>), grid, dim3(kThreads), (k1 > k2 ? k1 : k2) * 32, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((k_gemm_pair<16, 0>), grid, dim3(kThreads), 2 * 32 * 128 + 1024, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_gemm_pair launch", e);
+    return launched("k_gemm_pair launch");
 }
 
 void syn_debug_gemm_resident(int on) { g_gemm_resident = on; }     /* diagnostics: 0 = the streaming loop for the 16-row plain GEMMs too (A/B) */
@@ -2397,8 +2337,7 @@ int syn_test_handoff(uint32_t* sync_320_zeroed, uint32_t* buf_8x4096, const floa
     a.sync = sync_320_zeroed; a.buf = buf_8x4096; a.stream = stream; a.stream_n = stream_n; a.stale = stale_9_zeroed;
     a.words = words; a.rounds = rounds; a.mode = mode;
     hipLaunchKernelGGL(lat::k_handoff_stress, dim3(256), dim3(512), 96 * 1024, (hipStream_t)stream_h, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_handoff_stress launch", e);
+    return launched("k_handoff_stress launch");
 }
 
 int syn_train_stack_fwd(const syn_train_stack* t, void* stream) {
@@ -2423,8 +2362,7 @@ int syn_train_stack_fwd(const syn_train_stack* t, void* stream) {
     if (once.first()) { allow_lds(stk::k_stack_train, stk::kTrainLds); }
     const int grid = lat::kGroups * 4 * ((t->n_seq + lat::kGroups - 1) / lat::kGroups);
     hipLaunchKernelGGL(stk::k_stack_train, dim3(grid), dim3(kThreads), stk::kTrainLds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_stack_train launch", e);
+    return launched("k_stack_train launch");
 }
 
 int syn_train_stack_bwd(const syn_train_stack_grad* t, void* stream) {
@@ -2454,8 +2392,7 @@ int syn_train_stack_bwd(const syn_train_stack_grad* t, void* stream) {
     if (once.first()) { allow_lds(stk::k_stack_train_bwd, stk::kTrainBwdLds); }
     const int grid = lat::kGroups * 4 * ((f.n_seq + lat::kGroups - 1) / lat::kGroups);
     hipLaunchKernelGGL(stk::k_stack_train_bwd, dim3(grid), dim3(kThreads), stk::kTrainBwdLds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_stack_train_bwd launch", e);
+    return launched("k_stack_train_bwd launch");
 }
 
 // The weight gradients the backward chain left open: per block dW = dY^T . X for its four Linears - dY^T from syn_train_stack_bwd ([features][M] bf16),
@@ -2498,8 +2435,7 @@ int syn_train_stack_wgrad(const syn_train_stack_grad* t, void* stream) {
     // every block's four weight-gradient GEMMs in ONE launch (k_gemm_quad_all)
     hipLaunchKernelGGL(k_gemm_quad_all, dim3(q.cum[4] * (t->first_block - t->last_block + 1)), dim3(kThreads), lds, s, q);
     hipLaunchKernelGGL(stk::k_part_sums, dim3((stk::kPartCols + 255) / 256, t->first_block - t->last_block + 1), dim3(256), 0, s, f.n_seq, t->last_block, so);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_train_stack_wgrad", e);
+    return launched("syn_train_stack_wgrad");
 }
 
 int syn_test_mfma_rate(int32_t iters, float* out, int64_t* flops, void* stream) {
@@ -2509,24 +2445,21 @@ int syn_test_mfma_rate(int32_t iters, float* out, int64_t* flops, void* stream) 
     const int cus = device_cus();
     hipLaunchKernelGGL(seq::k_mfma_rate, dim3(cus), dim3(seq::kThreads), seq::kLds, (hipStream_t)stream, out, iters);
     if (flops) *flops = (int64_t)cus * 4 * (int64_t)iters * 16 * 12 * (2LL * 32 * 32 * 16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_mfma_rate launch", e);
+    return launched("k_mfma_rate launch");
 }
 
 int syn_test_attention(const void* q, const void* k, const void* vt, int32_t n_seq, void* o, void* stream) {
     if (!q || !k || !vt || !o || n_seq <= 0) return fail_msg("syn_test_attention: bad arguments");
     hipLaunchKernelGGL(k_attn, dim3(n_seq), dim3(256), 0, (hipStream_t)stream, (const __bf16*)q, (const __bf16*)k,
                        (const __bf16*)vt, (__bf16*)o, n_seq);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_attn launch", e);
+    return launched("k_attn launch");
 }
 
 // ---- training path: fp32 forward / backward of LayerNorm(512), GELU and the 32-token attention ---------------
 int syn_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* mean, float* rstd, int32_t rows, void* stream) {
     if (!x || !gamma || !beta || (!y && !y_bf16) || !mean || !rstd || rows <= 0) return fail_msg("syn_ln_fwd: bad arguments");
     hipLaunchKernelGGL(trn::k_ln_fwd, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, (__bf16*)y_bf16, mean, rstd, rows);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_ln_fwd launch", e);
+    return launched("k_ln_fwd launch");
 }
 
 int syn_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
@@ -2537,23 +2470,20 @@ int syn_ln_bwd(const float* dy, const float* x, const float* gamma, const float*
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(trn::k_ln_bwd, dim3(nwg), dim3(256), 0, s, dy, x, gamma, mean, rstd, add, dx, scratch, rows, per);
     hipLaunchKernelGGL(trn::k_colsum, dim3(4), dim3(256), 0, s, scratch, nwg, 2 * SYN_D, SYN_D, dgamma, dbeta);   // partials [p][dgamma | dbeta]
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_ln_bwd launch", e);
+    return launched("k_ln_bwd launch");
 }
 
 int syn_gelu_fwd(const float* x, float* y, void* y_bf16, int64_t n, void* stream) {
     if (!x || (!y && !y_bf16) || n <= 0 || n % 4) return fail_msg("syn_gelu_fwd: n must be a positive multiple of 4");
     hipLaunchKernelGGL(trn::k_gelu_fwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, (__bf16*)y_bf16, (size_t)(n / 4));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_gelu_fwd launch", e);
+    return launched("k_gelu_fwd launch");
 }
 
 int syn_linear_wgrad_rows(const float* dy, const void* x_bf16, int32_t m_rows, int32_t n, int32_t k, float* dw, float* db, void* stream) {
     if (!dy || !x_bf16 || !dw || m_rows <= 0 || m_rows > 64 || n <= 0 || n % 16 || k <= 0)
         return fail_msg("syn_linear_wgrad_rows: 1 .. 64 rows, n a multiple of 16");
     hipLaunchKernelGGL(trn::k_linear_wgrad_rows, dim3((k + 255) / 256, n / 16), dim3(256), 0, (hipStream_t)stream, dy, (const __bf16*)x_bf16, m_rows, n, k, dw, db);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_linear_wgrad_rows launch", e);
+    return launched("k_linear_wgrad_rows launch");
 }
 
 int syn_masked_smooth_l1(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
@@ -2564,8 +2494,7 @@ int syn_masked_smooth_l1(const float* target, const float* out, const uint8_t* m
     hipLaunchKernelGGL(glu::k_sl1_tiles<false>, dim3(chunks, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
                        (const float*)nullptr, part, (float*)nullptr);
     hipLaunchKernelGGL(glu::k_sl1_final, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, mask, batch, chunks, channels, t_len, poison_flag, loss);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_sl1_tiles launch", e);
+    return launched("k_sl1_tiles launch");
 }
 
 int syn_masked_smooth_l1_grad(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
@@ -2574,8 +2503,7 @@ int syn_masked_smooth_l1_grad(const float* target, const float* out, const uint8
         return fail_msg("syn_masked_smooth_l1_grad: channels must be a multiple of 64, t_len <= 64");
     hipLaunchKernelGGL(glu::k_sl1_tiles<true>, dim3(channels / 64, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
                        sample_scale, (float*)nullptr, dout);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_sl1_tiles (gradient) launch", e);
+    return launched("k_sl1_tiles (gradient) launch");
 }
 
 int syn_rows_concat_bf16(const syn_concat_src* srcs, int32_t n_src, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
@@ -2594,8 +2522,7 @@ int syn_rows_concat_bf16(const syn_concat_src* srcs, int32_t n_src, int32_t m_ro
     a.n_src = n_src; a.M = m_rows; a.out_ld = out_ld; a.out = (__bf16*)out_bf16;
     const long n = (long)m_rows * (out_ld / 4);
     hipLaunchKernelGGL(glu::k_rows_concat_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_rows_concat_bf16 launch", e);
+    return launched("k_rows_concat_bf16 launch");
 }
 
 int syn_embed_rows_bf16(const int64_t* ids, const float* table, int32_t vocab, int32_t dim, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
@@ -2603,37 +2530,32 @@ int syn_embed_rows_bf16(const int64_t* ids, const float* table, int32_t vocab, i
     const long n = (long)m_rows * (out_ld / 4);
     hipLaunchKernelGGL(glu::k_embed_rows_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long*>(ids), table, vocab,
                        dim, m_rows, out_ld, (__bf16*)out_bf16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_embed_rows_bf16 launch", e);
+    return launched("k_embed_rows_bf16 launch");
 }
 
 int syn_bct_to_rows_bf16(const float* x_bct, int32_t n_clips, int32_t channels, int32_t t_len, void* out_bf16, void* stream) {
     if (!x_bct || !out_bf16 || n_clips <= 0 || channels <= 0 || channels % 64 || t_len != 32) return fail_msg("syn_bct_to_rows_bf16: channels % 64 == 0, t_len == 32");
     hipLaunchKernelGGL(glu::k_bct_to_rows_bf16, dim3(channels / 64, n_clips), dim3(256), 0, (hipStream_t)stream, x_bct, channels, (__bf16*)out_bf16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_bct_to_rows_bf16 launch", e);
+    return launched("k_bct_to_rows_bf16 launch");
 }
 
 int syn_rows_group_sum(const float* src, int32_t ld, int32_t width, int32_t group, int32_t n_groups, float* out, void* stream) {
     if (!src || !out || ld < width || width <= 0 || group <= 0 || n_groups <= 0) return fail_msg("syn_rows_group_sum: bad arguments");
     hipLaunchKernelGGL(glu::k_rows_group_sum, dim3((n_groups * width + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, ld, width, group, n_groups, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_rows_group_sum launch", e);
+    return launched("k_rows_group_sum launch");
 }
 
 int syn_rows_expand(const float* src, int32_t ld, int32_t width, int32_t row_div, float scale, int32_t m_rows, float* out, void* stream) {
     if (!src || !out || width <= 0 || width % 4 || ld < width || ld % 4 || row_div < 1 || m_rows <= 0) return fail_msg("syn_rows_expand: width % 4 == 0, ld >= width, ld % 4 == 0, row_div >= 1");
     const long n = (long)m_rows * (width / 4);
     hipLaunchKernelGGL(glu::k_rows_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, ld, width, row_div, scale, m_rows, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_rows_expand launch", e);
+    return launched("k_rows_expand launch");
 }
 
 int syn_colsum_parts(const float* part, int32_t rows, int32_t n, float* out, void* stream) {
     if (!part || !out || rows <= 0 || n <= 0) return fail_msg("syn_colsum_parts: bad arguments");
     hipLaunchKernelGGL(glu::k_colsum_parts, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, part, rows, n, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_colsum_parts launch", e);
+    return launched("k_colsum_parts launch");
 }
 
 int syn_touch(const void* p, int64_t bytes, void* stream) {
@@ -2641,16 +2563,14 @@ int syn_touch(const void* p, int64_t bytes, void* stream) {
     const long lines = bytes / 64;
     const long blocks = (lines + 255) / 256;
     hipLaunchKernelGGL(glu::k_touch, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)p, lines, (unsigned*)nullptr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_touch launch", e);
+    return launched("k_touch launch");
 }
 
 int syn_rotary(const float* x, const float* cos_t, const float* sin_t, int32_t n_seq, int32_t inverse, float* y, void* stream) {
     if (!x || !cos_t || !sin_t || !y || n_seq <= 0) return fail_msg("syn_rotary: null pointer / empty batch");
     const long n_tok = (long)n_seq * SYN_T;
     hipLaunchKernelGGL(trn::k_rotary, dim3((unsigned)((n_tok * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, cos_t, sin_t, n_tok, inverse, y);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_rotary launch", e);
+    return launched("k_rotary launch");
 }
 
 int32_t syn_bn_chunks(int64_t rows) { const int cr = trn::bn_chunk_rows((long)rows); return (int32_t)((rows + cr - 1) / cr); }
@@ -2669,8 +2589,7 @@ int syn_bn_act_fwd(const float* y, const float* shortcut, int64_t rows, int32_t 
     const long n4 = rows * channels / 4;
     hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
                        act, z);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_act_fwd", e);
+    return launched("syn_bn_act_fwd");
 }
 
 int syn_bn_act_bwd(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
@@ -2685,8 +2604,7 @@ int syn_bn_act_bwd(const float* dz, const float* z, const float* y, const float*
     const long n4 = rows * channels / 4;
     hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)dgamma_dbeta,
                        channels, n4, (long)rows, act, dy, dshortcut);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_act_bwd", e);
+    return launched("syn_bn_act_bwd");
 }
 
 /* ---- the fused tail of a BasicBlock (syn_train.inc): statistics -> per-channel affine; one elementwise pass per block and direction ---- */
@@ -2697,8 +2615,7 @@ int syn_bn_finalize(const float* part, int32_t chunks, int64_t rows, int32_t cha
     if (!part || chunks <= 0 || !gamma || !beta || !stats || !affine || !bn_shape_ok(rows, channels)) return fail_msg("syn_bn_finalize: bad arguments");
     hipLaunchKernelGGL(trn::k_bn_finalize_aff, dim3(channels), dim3(256), 0, (hipStream_t)stream, part, chunks, channels, (long)rows, eps, momentum, gamma, beta,
                        stats, affine, run_mean, run_var, conv_bias);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_finalize", e);
+    return launched("syn_bn_finalize");
 }
 
 int syn_bn_finalize_pair(const syn_bn_finalize_job* a, const syn_bn_finalize_job* b, void* stream) {
@@ -2713,8 +2630,7 @@ int syn_bn_finalize_pair(const syn_bn_finalize_job* a, const syn_bn_finalize_job
         j[i].run_mean = q[i]->run_mean; j[i].run_var = q[i]->run_var; j[i].conv_bias = q[i]->conv_bias;
     }
     hipLaunchKernelGGL(trn::k_bn_finalize_aff2, dim3(j[0].C + j[1].C), dim3(256), 0, (hipStream_t)stream, j[0], j[1]);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_finalize_pair", e);
+    return launched("syn_bn_finalize_pair");
 }
 
 int syn_bn_apply2(const float* y, const float* affine, const float* shortcut, const float* short_affine, int64_t rows, int32_t channels, int32_t act,
@@ -2722,8 +2638,7 @@ int syn_bn_apply2(const float* y, const float* affine, const float* shortcut, co
     if (!y || !affine || !z || !bn_shape_ok(rows, channels) || (short_affine && !shortcut)) return fail_msg("syn_bn_apply2: bad arguments");
     const long n4 = rows * channels / 4;
     hipLaunchKernelGGL(trn::k_bn_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, affine, shortcut, short_affine, channels, n4, act, z);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_apply2", e);
+    return launched("syn_bn_apply2");
 }
 
 int syn_bn_block_bwd(const float* dz, const float* y, const float* shortcut, const float* stats, const float* affine, const float* short_stats,
@@ -2742,8 +2657,7 @@ int syn_bn_block_bwd(const float* dz, const float* y, const float* shortcut, con
     if (dy)                                                   // (dy NULL: the caller's next kernel forms dy / dshortcut itself - syn_conv1d_first_wgrad_tail)
         hipLaunchKernelGGL(trn::k_bn_bwd_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, y, shortcut, stats, affine, short_stats, short_affine,
                            (const float*)dgb, (const float*)short_dgb, channels, n4, (long)rows, act, dy, dshortcut);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_block_bwd", e);
+    return launched("syn_bn_block_bwd");
 }
 
 /* ---- nn.SyncBatchNorm on the same kernels: sums -> (the caller's all-reduce) -> apply ---- */
@@ -2754,8 +2668,7 @@ int syn_bn_sums(const float* y, int64_t rows, int32_t channels, float* ws, int32
     const int chunks = ws_chunks > 0 ? ws_chunks : syn_bn_chunks(rows);
     if (ws_chunks <= 0) hipLaunchKernelGGL(trn::k_bn_stats, dim3(chunks), dim3(256), 0, s, y, (long)rows, channels, ws);
     hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_sums", e);
+    return launched("syn_bn_sums");
 }
 
 int syn_bn_act_apply(const float* y, const float* shortcut, int64_t rows, int64_t rows_total, int32_t channels, const float* gamma, const float* beta,
@@ -2769,8 +2682,7 @@ int syn_bn_act_apply(const float* y, const float* shortcut, int64_t rows, int64_
     const long n4 = rows * channels / 4;
     hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
                        act, z);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_act_apply", e);
+    return launched("syn_bn_act_apply");
 }
 
 int syn_bn_bwd_sums(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
@@ -2782,8 +2694,7 @@ int syn_bn_bwd_sums(const float* dz, const float* z, const float* y, const float
     const int chunks = syn_bn_chunks(rows);
     hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
     hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_bwd_sums", e);
+    return launched("syn_bn_bwd_sums");
 }
 
 int syn_bn_act_bwd_apply(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta,
@@ -2797,8 +2708,7 @@ int syn_bn_act_bwd_apply(const float* dz, const float* z, const float* y, const 
     const long n4 = rows * channels / 4;
     hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)scratch,
                        channels, n4, (long)rows_total, act, dy, dshortcut);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_act_bwd_apply", e);
+    return launched("syn_bn_act_bwd_apply");
 }
 
 int syn_linear_bwd_prep(const float* dy, int32_t ld, int32_t row_div, float const_scale, int32_t m_rows, int32_t n, const float* row_scale,
@@ -2807,8 +2717,7 @@ int syn_linear_bwd_prep(const float* dy, int32_t ld, int32_t row_div, float cons
         return fail_msg("syn_linear_bwd_prep: need m_rows % 64 == 0, n % 64 == 0, ld >= n, ld % 4 == 0, row_div >= 1 and non-null pointers");
     hipLaunchKernelGGL(trn::k_linear_bwd_prep, dim3(n / 64, m_rows / 64), dim3(256), 0, (hipStream_t)stream, dy, ld, row_div, const_scale, m_rows, n, row_scale,
                        rows_per_scale, (__bf16*)dy_bf16, (__bf16*)dy_bf16_t, colsum_part);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_linear_bwd_prep launch", e);
+    return launched("k_linear_bwd_prep launch");
 }
 
 // ---- optimizer step (clip + Adam) over lists of <= 64 tensors ------------------------------------------------------------------------------------
@@ -2838,16 +2747,14 @@ int syn_opt_sqnorm(const syn_opt_list* l, float* partials, void* stream) {
     if (!partials) return fail_msg("syn_opt_sqnorm: partials is NULL");
     if (int rc = opt_fill(L, l, "syn_opt_sqnorm: need 1 .. 64 tensors with gradients")) return rc;
     hipLaunchKernelGGL(trn::k_opt_sqnorm, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, partials);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_opt_sqnorm launch", e);
+    return launched("k_opt_sqnorm launch");
 }
 
 int syn_opt_scalars(const float* partials, int32_t n_partials, float max_norm, const float* lr_dev, float lr, float beta1, float beta2, float* step_dev,
                     float* scal4, void* stream) {
     if ((n_partials > 0 && !partials) || n_partials < 0 || !step_dev || !scal4) return fail_msg("syn_opt_scalars: bad arguments");
     hipLaunchKernelGGL(trn::k_opt_scalars, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, max_norm, lr_dev, lr, beta1, beta2, step_dev, scal4);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_opt_scalars launch", e);
+    return launched("k_opt_scalars launch");
 }
 
 int syn_opt_adam(const syn_opt_list* l, const float* scal4, float beta1, float beta2, float eps, float weight_decay, void* stream) {
@@ -2856,8 +2763,7 @@ int syn_opt_adam(const syn_opt_list* l, const float* scal4, float beta1, float b
     if (int rc = opt_fill(L, l, "syn_opt_adam: need 1 .. 64 tensors")) return rc;
     for (int i = 0; i < L.n; ++i) if (!L.p[i] || !L.m[i] || !L.v[i]) return fail_msg("syn_opt_adam: null parameter / moment pointer");
     hipLaunchKernelGGL(trn::k_opt_adam, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, scal4, beta1, beta2, eps, weight_decay);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_opt_adam launch", e);
+    return launched("k_opt_adam launch");
 }
 
 int syn_embedding_wgrad(const int64_t* ids, const float* dy, int32_t ld, int32_t n_pos, int32_t vocab, int32_t dim, float* dw, void* stream) {
@@ -2865,22 +2771,19 @@ int syn_embedding_wgrad(const int64_t* ids, const float* dy, int32_t ld, int32_t
         return fail_msg("syn_embedding_wgrad: bad arguments (at most 8192 positions per call, vocab <= 65536, dim <= 512, ld >= dim)");
     hipLaunchKernelGGL(glu::k_embedding_wgrad, dim3((n_pos + glu::kEmbWaves - 1) / glu::kEmbWaves), dim3(glu::kEmbWaves * 64), 0, (hipStream_t)stream,
                        reinterpret_cast<const long*>(ids), dy, ld, n_pos, vocab, dim, dw);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_embedding_wgrad launch", e);
+    return launched("k_embedding_wgrad launch");
 }
 
 int syn_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
     if (!x || !dy || !dx || n <= 0 || n % 4) return fail_msg("syn_gelu_bwd: n must be a positive multiple of 4");
     hipLaunchKernelGGL(trn::k_gelu_bwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, (size_t)(n / 4));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_gelu_bwd launch", e);
+    return launched("k_gelu_bwd launch");
 }
 
 int syn_attn_fwd(const float* qkv, float* o, void* o_bf16, int32_t n_seq, void* stream) {
     if (!qkv || (!o && !o_bf16) || n_seq <= 0) return fail_msg("syn_attn_fwd: bad arguments");
     hipLaunchKernelGGL(trn::k_attn_fwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnFwd2Lds, (hipStream_t)stream, qkv, o, (__bf16*)o_bf16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_attn_fwd launch", e);
+    return launched("k_attn_fwd launch");
 }
 
 int syn_attn_bwd(const float* qkv, const float* d_o, float* dqkv, int32_t n_seq, void* stream) {
@@ -2888,8 +2791,7 @@ int syn_attn_bwd(const float* qkv, const float* d_o, float* dqkv, int32_t n_seq,
     static OncePerDevice once;
     if (once.first()) allow_lds(trn::k_attn_bwd2, trn::kAttnBwd2Lds);
     hipLaunchKernelGGL(trn::k_attn_bwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnBwd2Lds, (hipStream_t)stream, qkv, d_o, dqkv);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_attn_bwd launch", e);
+    return launched("k_attn_bwd launch");
 }
 
 int syn_cond_encode(const syn_cond_weights* w, const float* audio_feat, const int64_t* word, const float* seed, const float* style,
@@ -2904,8 +2806,7 @@ int syn_cond_encode(const syn_cond_weights* w, const float* audio_feat, const in
                        w->style_dim, w->st, n_clips, d_scratch);
     hipLaunchKernelGGL(cnd::k_cond_frames, dim3(SYN_D / 128, n_clips), dim3(256), 0, s, audio_feat, (const long long*)word, w->gt, w->tw,
                        w->vocab, d_scratch, w->c0, n_clips, cond);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_cond_encode", e);
+    return launched("syn_cond_encode");
 }
 
 int32_t syn_wav_out_frames(int32_t n_samples) { return n_samples >= 15 ? wav_plan(n_samples).L4 : 0; }
@@ -2967,8 +2868,7 @@ int syn_wav_encode(const syn_wavenc* enc, const float* wav_in, int32_t n_clips, 
     if ((rc = launch_conv<384, 5, 8, 1, 4, wav::E_C1SC>(a, n_clips, s))) return rc;
     a = base(10); a.X = ws + p.z5; a.x_rows = p.L4 + 2 * kHalo; a.L_out = p.L4; a.R = ws + p.s5; a.Yf = out; a.yf_clip_stride = (long)p.L4 * 256;
     if ((rc = launch_conv<256, 15, 4, 1, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_wav_encode", e);
+    return launched("syn_wav_encode");
 }
 
 // output-channel tile of the strided layers' weight gradient (k_conv_wgrad_s<CO_T, TAPS>; conv_train_wgrad_impl launches what this says)
@@ -3019,8 +2919,7 @@ static int conv_train_wgrad_impl(const float* x, const float* dy, int32_t n_clip
     if (rc || !dw) return rc;                                    // (dw NULL: the partial sums only - syn_conv1d_wgrad_sums adds several gradients' up in one launch)
     const int total4 = cout * taps * cinp / 4;                   // (cin % 16 == 0: four consecutive channels share r)
     hipLaunchKernelGGL(wav::k_conv_wgrad_sum, dim3((total4 + 31) / 32), dim3(256), 0, s, (const float*)ws, a.shares, cout, cin, stride, taps, dw);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_wgrad_sum launch", e);
+    return launched("k_conv_wgrad_sum launch");
 }
 
 int syn_conv1d_train_wgrad(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
@@ -3084,8 +2983,7 @@ int syn_conv1d_first_fwd_stats(const float* x, int32_t n_clips, int32_t l_in, in
     if (lds < 4 * 2 * 64 * sizeof(float)) lds = 4 * 2 * 64 * sizeof(float);       // (the statistics of the four position groups meet in the window's place)
     if (cin == 1) hipLaunchKernelGGL(wav::k_conv_first_fwd<1>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(wav::k_conv_first_fwd<2>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_first_fwd launch", e);
+    return launched("k_conv_first_fwd launch");
 }
 
 int syn_conv1d_first_fwd(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, const float* w, float* y,
@@ -3120,8 +3018,7 @@ static int first_wgrad_impl(const float* x, const float* dy, const float* bn_y, 
     else hipLaunchKernelGGL((wav::k_conv_first_wgrad_m<2>), dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
     const int n = 64 * cin * 15;
     if (dw) hipLaunchKernelGGL(wav::k_conv_first_wsum, dim3((n + 63) / 64), dim3(1024), 0, s, (const float*)ws, groups, n, dw);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_first_wgrad_m launch", e);
+    return launched("k_conv_first_wgrad_m launch");
 }
 
 int syn_conv1d_wgrad_sums(const syn_wgrad_sum_job* jobs, int32_t n_jobs, void* stream) {
@@ -3149,8 +3046,7 @@ int syn_conv1d_wgrad_sums(const syn_wgrad_sum_job* jobs, int32_t n_jobs, void* s
     }
     a.n = n_jobs;
     hipLaunchKernelGGL(wav::k_conv_wgrad_sums, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_wgrad_sums launch", e);
+    return launched("k_conv_wgrad_sums launch");
 }
 
 int syn_conv1d_first_wgrad(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws,
@@ -3181,8 +3077,7 @@ int syn_conv1d_first_wgrad_bn_lin(const float* x, const float* dz, const float* 
         hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin<2>, dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
         hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin_fin<2>, dim3(64), dim3(1024), 0, s, (const float*)ws, groups, affine, inv_rows, dw, dgamma_dbeta);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_first_wgrad_lin launch", e);
+    return launched("k_conv_first_wgrad_lin launch");
 }
 
 int syn_conv1d_first_wgrad_tail(const float* x, const float* dout, const float* y2, const float* y_short, const float* stats2, const float* affine2,
@@ -3203,8 +3098,7 @@ int syn_conv1d_first_fwd2(const float* x, int32_t n_clips, int32_t l_in, int32_t
     if (lds < 2 * 4 * 2 * 64 * sizeof(float)) lds = 2 * 4 * 2 * 64 * sizeof(float);
     if (cin == 1) hipLaunchKernelGGL(wav::k_conv_first_fwd2<1>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(wav::k_conv_first_fwd2<2>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_first_fwd2 launch", e);
+    return launched("k_conv_first_fwd2 launch");
 }
 
 // backward statistics of a BatchNorm (+ activation) alone - dgamma_dbeta [3][channels] - for a consumer that forms dy itself (syn_conv1d_first_wgrad_bn)
@@ -3216,8 +3110,7 @@ int syn_bn_bwd_stats(const float* dz, const float* z, const float* y, const floa
     const int chunks = syn_bn_chunks(rows);
     hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
     hipLaunchKernelGGL(trn::k_bn_bwd_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgamma_dbeta);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_bn_bwd_stats", e);
+    return launched("syn_bn_bwd_stats");
 }
 
 // taps of the strided data-gradient GEMM, padded so that taps * cout / 32 is a multiple of the weight ring's 3
@@ -3254,8 +3147,7 @@ int syn_conv1d_pack_split_many(const syn_conv_pack_req* reqs, int32_t n_reqs, vo
         most = total > most ? total : most;
     }
     hipLaunchKernelGGL(k_conv_pack_split_many, dim3((most + 255) / 256, n_reqs), dim3(256), 0, (hipStream_t)stream, j);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_pack_split_many launch", e);
+    return launched("k_conv_pack_split_many launch");
 }
 
 int syn_conv1d_pack_split(const float* w, int32_t cout, int32_t cin, int32_t stride, int32_t transposed, void* out_hi, void* out_lo,
@@ -3266,8 +3158,7 @@ int syn_conv1d_pack_split(const float* w, int32_t cout, int32_t cin, int32_t str
     if (total < 0) return fail_msg("syn_conv1d_pack_split: channels must be multiples of 16 and taps x channels a multiple of 32");
     hipLaunchKernelGGL(k_conv_pack_split, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, cout, cin, kts, mode, stride,
                        (uint4*)out_hi, (uint4*)out_lo);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_conv_pack_split launch", e);
+    return launched("k_conv_pack_split launch");
 }
 
 int64_t syn_conv1d_pack_bytes(int32_t cout, int32_t cin, int32_t stride, int32_t transposed) {
@@ -3421,6 +3312,193 @@ struct StageTimer {          // optional hipEvent after every launch
 // Start-delay spread of a multi-step k_seq launch, in units of 64 cycles across the grid (syn_seq.inc); diagnostics only.
 static int g_seq_skew = -1, g_seq_dbg_step = 0;
 
+// ---- one denoising step: validate -> plan_step (syn_step_plan.inc) -> run_seq / run_lat / run_stack / run_layers ---------------------
+struct StepCall {            // what every path of a step is handed
+    const syn_model* md;
+    const syn_step* st;
+    const syn_edit* ed;      // in-painting, or nullptr: the four token-major output stages blend it in (syn_denoise_step_edit has refused
+                             // the wave-per-sequence kernel, which has no such operand)
+    hipStream_t s;
+    StageTimer* tm;
+    void mark(int c) const { if (tm) tm->mark(c); }
+    const unsigned char* keep() const { return ed ? ed->keep : nullptr; }
+    const float* known() const { return ed ? ed->known : nullptr; }
+};
+
+// k_seq: one wave per sequence, weights streamed once per 128 rows (syn_seq.inc); n_steps > 1: the persistent step loop
+static int run_seq(const StepCall& c, int n_steps, int tm_stride, int tc_stride) {
+    const syn_model* md = c.md; const syn_step* st = c.st;
+    if (!md->tape || !md->tape_bias) return fail_msg("syn_denoise_step: syn_model.tape is not set");
+    if (md->tape_chunks * seq::kChunkFrags != 36096) return fail_msg("syn_denoise_step: syn_model.tape_chunks must count 16-fragment chunks of the 36096-fragment tape (2256)");
+    seq::QArgs q;
+    memset(&q, 0, sizeof(q));
+    q.tape = (const char*)md->tape; q.tape_chunks = (unsigned)md->tape_chunks; q.bias = md->tape_bias;
+    q.te = md->te; q.rcos = md->rot_cos; q.rsin = md->rot_sin; q.cond = st->cond; q.t_model = st->t_model;
+    q.xt = st->x_t; q.xb = (const uint4*)st->x_t_bf16; q.noise = st->noise; q.rng = (const unsigned long long*)st->rng;
+    q.coef = st->coef; q.t_coef = st->t_coef; q.xn = st->x_next; q.xnb = (uint4*)st->x_next_bf16; q.x0 = st->pred_x0;
+    q.R = st->n_clips; q.V = st->n_variants; q.cfg_w = st->cfg_w; q.cfg_stride = st->cfg_w_clip_stride; q.dbg = g_dbg_mlp;
+    q.n_steps = n_steps; q.tm_stride = tm_stride; q.tc_stride = tc_stride; q.dbg_step = g_seq_dbg_step;
+    if (n_steps > 1 && st->noise) return fail_msg("syn_denoise_steps: injected noise is per step - run such steps one by one");
+    // The persistent step loop wants all its workgroups resident at once (one per CU).  A larger batch goes out as
+    // CU-filling slices, each carried through ALL the steps by its own launch (slices are independent: a sequence never
+    // leaves its wave); run as one launch, a round of workgroups would finish all its steps before the next one starts
+    // and the ragged ends of the rounds add up (measured: -1.7 % at 2048 clips, -2.2 % at 4096 against single steps).
+    const int total = seq_grid(q.R, q.V), cus = device_cus();
+    if (n_steps > 1 && total > cus) {
+        for (int w0 = 0; w0 < total; w0 += cus) {
+            q.wg0 = w0; q.n_wg = total - w0 < cus ? total - w0 : cus;
+            if (int rc = launch_seq(q, c.s)) return rc;
+        }
+        c.mark(ST_FC2);
+        return launched("syn_denoise_steps");
+    }
+    q.skew = n_steps > 1 && g_seq_skew > 0 ? (unsigned)g_seq_skew : 0u;      // (diagnostics: imposed start delays, see k_seq)
+    if (int rc = launch_seq(q, c.s)) return rc;
+    c.mark(ST_FC2);
+    return launched("syn_denoise_step");
+}
+
+// k_lat: one persistent kernel, output features split over the CUs of an XCD (syn_latency.inc); by_seq: the variants of a guided batch
+// leave their x0_hat in ws_x0v and k_guided_update combines them
+static int run_lat(const StepCall& c, bool by_seq) {
+    const syn_model* md = c.md; const syn_step* st = c.st;
+    lat::LArgs la;
+    memset(&la, 0, sizeof(la));
+    la.w_in = (const uint4*)md->w_in; la.te = md->te; la.rcos = md->rot_cos; la.rsin = md->rot_sin;
+    for (int l = 0; l < SYN_LAYERS; ++l) la.layer[l] = md->layer[l];
+    la.w_out = (const uint4*)md->w_out; la.b_out = md->b_out;
+    la.B = st->n_clips; la.V = st->n_variants;
+    la.cond = st->cond; la.t_model = st->t_model; la.cfg_w = st->cfg_w; la.cfg_stride = st->cfg_w_clip_stride;
+    la.xb = (const __bf16*)st->x_t_bf16; la.xt = st->x_t; la.noise = st->noise;
+    la.rng = (const unsigned long long*)st->rng; la.coef = st->coef; la.t_coef = st->t_coef;
+    la.xn = st->x_next; la.xnb = (__bf16*)st->x_next_bf16; la.x0 = st->pred_x0;
+    la.keep = c.keep(); la.known = c.known();
+    la.H = st->ws_h; la.Q = (__bf16*)st->ws_q; la.Kb = (__bf16*)st->ws_k; la.Vt = (__bf16*)st->ws_vt;
+    la.HID = (__bf16*)st->ws_hid; la.sync = st->ws_sync; la.dbg = g_dbg_mlp;
+    la.X0v = by_seq ? st->ws_x0v : nullptr;
+    if (int rc = launch_latency(la, c.s)) return rc;
+    c.mark(ST_FC2);
+    if (by_seq) {
+        UArgs u;
+        u.X0v = st->ws_x0v; u.w = st->cfg_w; u.w_stride = st->cfg_w_clip_stride; u.V = st->n_variants; u.B = st->n_clips; u.Xt = st->x_t; u.noise = st->noise;
+        u.rng = (const unsigned long long*)st->rng; u.coef = st->coef; u.t_coef = st->t_coef;
+        u.Xn = st->x_next; u.Xnb = (__bf16*)st->x_next_bf16; u.X0 = st->pred_x0;
+        u.keep = c.keep(); u.known = c.known();
+        const size_t n4 = (size_t)st->n_clips * SYN_T * SYN_C / 4;
+        hipLaunchKernelGGL(k_guided_update, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, c.s, u);
+        c.mark(ST_OUT);
+    }
+    return launched("syn_denoise_step");
+}
+
+// input stage of the token-major paths: h = rotary(x_t A^T + cond + te[t])
+static GArgs step_in_args(const StepCall& c) {
+    const syn_model* md = c.md; const syn_step* st = c.st;
+    const int Mb = st->n_clips * SYN_T;
+    GArgs ain;
+    memset(&ain, 0, sizeof(ain));
+    ain.X = (const __bf16*)st->x_t_bf16; ain.ldx = SYN_C; ain.x_rows = Mb; ain.W = (const uint4*)md->w_in; ain.K = SYN_C; ain.M = st->n_variants * Mb;
+    ain.cond = st->cond; ain.te = md->te; ain.t_model = st->t_model; ain.rcos = md->rot_cos; ain.rsin = md->rot_sin;
+    ain.H = st->ws_h; ain.ldy = SYN_D;
+    return ain;
+}
+
+// output stage of the token-major paths (its input X is set by whoever runs it: k_stack itself, or step_out_stage)
+static GArgs step_out_args(const StepCall& c) {
+    const syn_model* md = c.md; const syn_step* st = c.st;
+    const int Mb = st->n_clips * SYN_T;
+    GArgs aout;
+    memset(&aout, 0, sizeof(aout));
+    aout.ldx = SYN_D; aout.x_rows = Mb; aout.W = (const uint4*)md->w_out; aout.K = SYN_D; aout.M = Mb; aout.bias = md->b_out;
+    aout.Xt = st->x_t; aout.noise = st->noise; aout.rng = (const unsigned long long*)st->rng; aout.coef = st->coef;
+    aout.t_coef = st->t_coef; aout.Xn = st->x_next; aout.Xnb = (__bf16*)st->x_next_bf16; aout.X0 = st->pred_x0;
+    aout.keep = c.keep(); aout.known = c.known();
+    return aout;
+}
+
+static int step_out_stage(const StepCall& c, int out_tile);
+
+// k_stack: the whole stack in one kernel (production), the output stage inside it when there is a single conditioning variant
+static int run_stack(const StepCall& c, const StepPlan& p) {
+    const syn_step* st = c.st;
+    SArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.H = st->ws_h; sa.Y = (__bf16*)st->ws_xn; sa.M = st->n_variants * st->n_clips * SYN_T; sa.write_h = st->n_variants > 1; sa.dbg = g_dbg_mlp;
+    for (int l = 0; l < SYN_LAYERS; ++l) sa.layer[l] = c.md->layer[l];
+    sa.in = step_in_args(c);
+    if (p.fuse_out) sa.out = step_out_args(c);
+    sa.tp = p.tp;
+    if (p.tp > 1) { sa.tp_tiles = st->n_variants * st->n_clips; sa.sync = st->ws_sync; sa.xch = st->ws_xch; }
+    if (int rc = launch_stack(sa, p.tile_rows, c.s)) return rc;
+    c.mark(ST_FC2);
+    return p.fuse_out ? launched("syn_denoise_step") : step_out_stage(c, p.out_tile);
+}
+
+// five kernels per block, kept as the plain restatement the whole-stack kernel is checked against bit for bit (tests) and for the h8 tap
+// it leaves in ws_xn
+static int run_layers(const StepCall& c, const StepPlan& p) {
+    const syn_model* md = c.md; const syn_step* st = c.st;
+    hipStream_t s = c.s;
+    const int R = st->n_variants * st->n_clips * SYN_T, mt = p.tile_rows;
+    int rc;
+    GArgs a = step_in_args(c);           // [; xn = LN1_0(h)]
+    a.Y = (__bf16*)st->ws_xn; a.ln_g = md->layer[0].ln1_g; a.ln_b = md->layer[0].ln1_b;
+    if ((rc = launch_gemm<EPI_IN>(a, mt, 1, s))) return rc;
+    c.mark(ST_IN);
+    for (int l = 0; l < SYN_LAYERS; ++l) {
+        const syn_layer& L = md->layer[l];
+        // qkv
+        memset(&a, 0, sizeof(a));
+        a.X = (const __bf16*)st->ws_xn; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_qkv; a.K = SYN_D; a.M = R;
+        a.Q = (__bf16*)st->ws_q; a.Kb = (__bf16*)st->ws_k; a.Vt = (__bf16*)st->ws_vt;
+        if ((rc = launch_gemm<EPI_QKV>(a, mt, 3, s))) return rc;
+        c.mark(ST_QKV);
+        // attention
+        hipLaunchKernelGGL(k_attn, dim3(R / SYN_T), dim3(256), 0, s, (const __bf16*)st->ws_q, (const __bf16*)st->ws_k,
+                           (const __bf16*)st->ws_vt, (__bf16*)st->ws_o, R / SYN_T);
+        c.mark(ST_ATTN);
+        // proj + residual, LN2 -> xn
+        memset(&a, 0, sizeof(a));
+        a.X = (const __bf16*)st->ws_o; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_proj; a.K = SYN_D; a.M = R;
+        a.bias = L.b_proj; a.H = st->ws_h; a.Y = (__bf16*)st->ws_xn; a.ldy = SYN_D; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b;
+        if ((rc = launch_gemm<EPI_RESID>(a, mt, 1, s))) return rc;
+        c.mark(ST_PROJ);
+        // fc1 + gelu
+        memset(&a, 0, sizeof(a));
+        a.X = (const __bf16*)st->ws_xn; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_fc1; a.K = SYN_D; a.M = R;
+        a.bias = L.b_fc1; a.Y = (__bf16*)st->ws_hid; a.ldy = SYN_FF;
+        if ((rc = launch_gemm<EPI_GELU>(a, mt, 2, s))) return rc;
+        c.mark(ST_FC1);
+        // fc2 + residual, next block's LN1 -> xn (last block: plain bf16 copy, there is no final norm)
+        memset(&a, 0, sizeof(a));
+        a.X = (const __bf16*)st->ws_hid; a.ldx = SYN_FF; a.x_rows = R; a.W = (const uint4*)L.w_fc2; a.K = SYN_FF; a.M = R;
+        a.bias = L.b_fc2; a.H = st->ws_h; a.Y = (__bf16*)st->ws_xn; a.ldy = SYN_D;
+        if (l + 1 < SYN_LAYERS) { a.ln_g = md->layer[l + 1].ln1_g; a.ln_b = md->layer[l + 1].ln1_b; }
+        if ((rc = launch_gemm<EPI_RESID>(a, mt, 1, s))) return rc;
+        c.mark(ST_FC2);
+    }
+    return step_out_stage(c, p.out_tile);
+}
+
+// the separate output stage (+ guidance combination of the variants, linear so it commutes with the GEMM)
+static int step_out_stage(const StepCall& c, int out_tile) {
+    const syn_step* st = c.st;
+    const int Mb = st->n_clips * SYN_T;
+    GArgs aout = step_out_args(c);
+    if (st->n_variants > 1) {
+        const size_t n4 = (size_t)3 * Mb * kNT / 4;
+        hipLaunchKernelGGL(k_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, c.s, st->ws_h, st->cfg_w, st->cfg_w_clip_stride, st->n_variants, Mb,
+                           (__bf16*)st->ws_hc);
+        c.mark(ST_COMBINE);
+        aout.X = (const __bf16*)st->ws_hc; aout.x_chunk_stride = (long)Mb * kNT;
+    } else {
+        aout.X = (const __bf16*)st->ws_xn;
+    }
+    if (int rc = launch_gemm<EPI_OUT>(aout, out_tile, 3, c.s)) return rc;
+    c.mark(ST_OUT);
+    return launched("syn_denoise_step");
+}
+
 static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, StageTimer* tm, int n_steps = 1, int tm_stride = 0,
                      int tc_stride = 0, const syn_edit* ed = nullptr) {
     if (!md || !st) return fail_msg("syn_denoise_step: null model/step");
@@ -3431,191 +3509,17 @@ static int step_impl(const syn_model* md, const syn_step* st, hipStream_t s, Sta
     if (!st->cond || !st->t_model || !st->x_t || !st->x_t_bf16 || !st->coef || !st->t_coef || !st->x_next ||
         !st->x_next_bf16 || !st->ws_h || !st->ws_xn || !st->ws_q || !st->ws_k || !st->ws_vt || !st->ws_o || !st->ws_hid)
         return fail_msg("syn_denoise_step: null state/workspace pointer");
-    const int Mb = B * SYN_T, R = V * Mb;
-    const int mt = st->m_tile ? st->m_tile : pick_tile(R);
-    int rc;
-    GArgs a;
-    auto mark = [&](int c) { if (tm) tm->mark(c); };
-
-    // in-painting: the four token-major output stages blend it in (syn_denoise_step_edit has refused the wave-per-sequence kernel, which has
-    // no such operand)
-    const unsigned char* const keep = ed ? ed->keep : nullptr;
-    const float* const known = ed ? ed->known : nullptr;
-
-    if (st->x_fragment_order || (st->reserved & 7) == 5) {
-        // large single-variant batches: one wave per sequence, weights streamed once per 128 rows (syn_seq.inc)
-        if (!st->x_fragment_order) return fail_msg("syn_denoise_step: the wave-per-sequence kernel needs the latent in fragment order (x_fragment_order = 1)");
-        if (V > 4) return fail_msg("syn_denoise_step: fragment-order latents take at most 4 variants per clip (a clip's variants are the waves of one workgroup)");
-        if (!md->tape || !md->tape_bias) return fail_msg("syn_denoise_step: syn_model.tape is not set");
-        if (md->tape_chunks * seq::kChunkFrags != 36096) return fail_msg("syn_denoise_step: syn_model.tape_chunks must count 16-fragment chunks of the 36096-fragment tape (2256)");
-        seq::QArgs q;
-        memset(&q, 0, sizeof(q));
-        q.tape = (const char*)md->tape; q.tape_chunks = (unsigned)md->tape_chunks; q.bias = md->tape_bias;
-        q.te = md->te; q.rcos = md->rot_cos; q.rsin = md->rot_sin; q.cond = st->cond; q.t_model = st->t_model;
-        q.xt = st->x_t; q.xb = (const uint4*)st->x_t_bf16; q.noise = st->noise; q.rng = (const unsigned long long*)st->rng;
-        q.coef = st->coef; q.t_coef = st->t_coef; q.xn = st->x_next; q.xnb = (uint4*)st->x_next_bf16; q.x0 = st->pred_x0;
-        q.R = B; q.V = V; q.cfg_w = st->cfg_w; q.cfg_stride = st->cfg_w_clip_stride; q.dbg = g_dbg_mlp;
-        // The persistent step loop wants all its workgroups resident at once (one per CU).  A larger batch goes out as
-        // CU-filling slices, each carried through ALL the steps by its own launch (slices are independent: a sequence never
-        // leaves its wave); run as one launch, a round of workgroups would finish all its steps before the next one starts
-        // and the ragged ends of the rounds add up (measured: -1.7 % at 2048 clips, -2.2 % at 4096 against single steps).
-        if (n_steps > 1 && st->noise) return fail_msg("syn_denoise_steps: injected noise is per step - run such steps one by one");
-        if (n_steps > 1 && seq_grid(B, V) > device_cus()) {
-            q.n_steps = n_steps; q.tm_stride = tm_stride; q.tc_stride = tc_stride; q.dbg_step = g_seq_dbg_step; q.skew = 0;
-            const int total = seq_grid(B, V), cus = device_cus();
-            for (int w0 = 0; w0 < total; w0 += cus) {
-                q.wg0 = w0; q.n_wg = total - w0 < cus ? total - w0 : cus;
-                if ((rc = launch_seq(q, s))) return rc;
-            }
-            mark(ST_FC2);
-            hipError_t e2 = hipGetLastError();
-            return e2 == hipSuccess ? 0 : fail("syn_denoise_steps", e2);
-        }
-        q.n_steps = n_steps; q.tm_stride = tm_stride; q.tc_stride = tc_stride; q.dbg_step = g_seq_dbg_step;
-        q.skew = n_steps > 1 && g_seq_skew > 0 ? (unsigned)g_seq_skew : 0u;      // (diagnostics: imposed start delays, see k_seq)
-        if ((rc = launch_seq(q, s))) return rc;
-        mark(ST_FC2);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail("syn_denoise_step", e);
+    const StepPlan p = plan_step({B, V, st->m_tile, st->reserved, st->x_fragment_order, st->ws_sync != nullptr, st->ws_xch != nullptr,
+                                  st->ws_x0v != nullptr, device_cus(), latency_path_ok()});
+    const StepCall c{md, st, ed, s, tm};
+    switch (p.path) {
+        case STEP_SEQ:    return run_seq(c, n_steps, tm_stride, tc_stride);
+        case STEP_LAT:    return run_lat(c, p.by_seq);
+        case STEP_STACK:  return run_stack(c, p);
+        case STEP_LAYERS: return run_layers(c, p);
+        case STEP_ERROR:  break;
     }
-    int mode = st->reserved & 3;
-    if (mode == 2) return fail_msg("syn_denoise_step: kernel selection 2 (two kernels per block) was removed in ABI 8; 1 = the per-operation path");
-    // Small batches: the persistent feature-split kernel (syn_latency.inc) beats the token-resident one while a
-    // group (XCD) holds at most 4 sequences (measured per step: 161 / 239 / 405 us at 1 / 2 / 4 sequences per
-    // group against ~445 us, and 733 us at 8).  Guided batches (V > 1) deal SEQUENCES to the XCDs when the caller
-    // provides ws_x0v (each variant's x0_hat is produced on its own XCD, k_guided_update combines them), else whole
-    // clips with all their variants.  reserved bit 2 pins the whole-step kernel (A/B runs, bitwise cross-checks
-    // against layer modes 1 / 2).
-    const bool by_seq = V > 1 && st->ws_x0v != nullptr;
-    const int per_group = by_seq ? (B * V + lat::kGroups - 1) / lat::kGroups : ((B + lat::kGroups - 1) / lat::kGroups) * V;
-    // 9..128 sequences (measured: 216-231 us per step at 9..48 sequences, 270 at 64, 312-337 us at 65..128, against
-    // 235-400 us of the small-batch kernel at 9..32 and 405-413 us of one workgroup per tile above): the whole-step kernel with every
-    // 32-row tile split over 4 (<= 64 sequences) or 2 workgroups of one XCD, see k_stack.  reserved bit 3 (value 8)
-    // switches it off, and so does pinning a kernel (bit 2) or a tile size.
-    const int tiles = V * B;
-    // (129..256 sequences as 64-row tiles split over 2 workgroups: measured in round 5 and slower than one 32-row tile per CU - lab notebook)
-    const bool use_tp = mode == 0 && st->m_tile == 0 && !(st->reserved & 12) && st->ws_sync && st->ws_xch &&
-                        tiles >= 9 && tiles <= 128 && latency_path_ok();
-    if (mode == 0 && !use_tp && !(st->reserved & 4) && st->ws_sync && per_group <= 4 && latency_path_ok()) mode = 3;
-    if (mode == 3) {
-        // small-batch path: one persistent kernel, output features split over the CUs of an XCD
-        if (!st->ws_sync) return fail_msg("syn_denoise_step: the latency path needs ws_sync");
-        if (!latency_path_ok()) return fail_msg("syn_denoise_step: the latency path needs a 256-CU (8 XCD x 32) device");
-        lat::LArgs la;
-        memset(&la, 0, sizeof(la));
-        la.w_in = (const uint4*)md->w_in; la.te = md->te; la.rcos = md->rot_cos; la.rsin = md->rot_sin;
-        for (int l = 0; l < SYN_LAYERS; ++l) la.layer[l] = md->layer[l];
-        la.w_out = (const uint4*)md->w_out; la.b_out = md->b_out;
-        la.B = B; la.V = V;
-        la.cond = st->cond; la.t_model = st->t_model; la.cfg_w = st->cfg_w; la.cfg_stride = st->cfg_w_clip_stride;
-        la.xb = (const __bf16*)st->x_t_bf16; la.xt = st->x_t; la.noise = st->noise;
-        la.rng = (const unsigned long long*)st->rng; la.coef = st->coef; la.t_coef = st->t_coef;
-        la.xn = st->x_next; la.xnb = (__bf16*)st->x_next_bf16; la.x0 = st->pred_x0;
-        la.keep = keep; la.known = known;
-        la.H = st->ws_h; la.Q = (__bf16*)st->ws_q; la.Kb = (__bf16*)st->ws_k; la.Vt = (__bf16*)st->ws_vt;
-        la.HID = (__bf16*)st->ws_hid; la.sync = st->ws_sync; la.dbg = g_dbg_mlp;
-        la.X0v = by_seq ? st->ws_x0v : nullptr;
-        if ((rc = launch_latency(la, s))) return rc;
-        mark(ST_FC2);
-        if (by_seq) {
-            UArgs u;
-            u.X0v = st->ws_x0v; u.w = st->cfg_w; u.w_stride = st->cfg_w_clip_stride; u.V = V; u.B = B; u.Xt = st->x_t; u.noise = st->noise;
-            u.rng = (const unsigned long long*)st->rng; u.coef = st->coef; u.t_coef = st->t_coef;
-            u.Xn = st->x_next; u.Xnb = (__bf16*)st->x_next_bf16; u.X0 = st->pred_x0;
-            u.keep = keep; u.known = known;
-            const size_t n4 = (size_t)B * SYN_T * SYN_C / 4;
-            hipLaunchKernelGGL(k_guided_update, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, u);
-            mark(ST_OUT);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail("syn_denoise_step", e);
-    }
-    // input stage: h = rotary(x_t A^T + cond + te[t]) [; xn = LN1_0(h) for the unfused A/B paths]
-    GArgs ain;
-    memset(&ain, 0, sizeof(ain));
-    ain.X = (const __bf16*)st->x_t_bf16; ain.ldx = SYN_C; ain.x_rows = Mb; ain.W = (const uint4*)md->w_in; ain.K = SYN_C; ain.M = R;
-    ain.cond = st->cond; ain.te = md->te; ain.t_model = st->t_model; ain.rcos = md->rot_cos; ain.rsin = md->rot_sin;
-    ain.H = st->ws_h; ain.ldy = SYN_D;
-    if (mode != 0) {
-        ain.Y = (__bf16*)st->ws_xn; ain.ln_g = md->layer[0].ln1_g; ain.ln_b = md->layer[0].ln1_b;
-        if ((rc = launch_gemm<EPI_IN>(ain, mt, 1, s))) return rc;
-        mark(ST_IN);
-    }
-    // output stage arguments (fused into the step kernel when there is a single conditioning variant)
-    GArgs aout;
-    memset(&aout, 0, sizeof(aout));
-    aout.ldx = SYN_D; aout.x_rows = Mb; aout.W = (const uint4*)md->w_out; aout.K = SYN_D; aout.M = Mb; aout.bias = md->b_out;
-    aout.Xt = st->x_t; aout.noise = st->noise; aout.rng = (const unsigned long long*)st->rng; aout.coef = st->coef;
-    aout.t_coef = st->t_coef; aout.Xn = st->x_next; aout.Xnb = (__bf16*)st->x_next_bf16; aout.X0 = st->pred_x0;
-    aout.keep = keep; aout.known = known;
-    const bool fuse_out = mode == 0 && V == 1;
-
-    // layer implementation: 0 = whole stack in one kernel (production); 1 = five kernels per block, kept as the plain restatement the whole-stack kernel is
-    // checked against bit for bit (tests) and for the h8 tap it leaves in ws_xn.
-    if (mode == 0) {
-        SArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.H = st->ws_h; sa.Y = (__bf16*)st->ws_xn; sa.M = R; sa.write_h = V > 1; sa.dbg = g_dbg_mlp;
-        for (int l = 0; l < SYN_LAYERS; ++l) sa.layer[l] = md->layer[l];
-        sa.in = ain;
-        if (fuse_out) sa.out = aout;
-        int tile_rows = mt > 64 ? 64 : mt;
-        sa.tp = 1;
-        if (use_tp) {
-            sa.tp = tiles <= 64 ? 4 : 2; sa.tp_tiles = tiles; sa.sync = st->ws_sync; sa.xch = st->ws_xch; tile_rows = 32;
-        }
-        if ((rc = launch_stack(sa, tile_rows, s))) return rc;
-        mark(ST_FC2);
-    } else
-    for (int l = 0; l < SYN_LAYERS; ++l) {
-        const syn_layer& L = md->layer[l];
-        // qkv
-        memset(&a, 0, sizeof(a));
-        a.X = (const __bf16*)st->ws_xn; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_qkv; a.K = SYN_D; a.M = R;
-        a.Q = (__bf16*)st->ws_q; a.Kb = (__bf16*)st->ws_k; a.Vt = (__bf16*)st->ws_vt;
-        if ((rc = launch_gemm<EPI_QKV>(a, mt, 3, s))) return rc;
-        mark(ST_QKV);
-        // attention
-        hipLaunchKernelGGL(k_attn, dim3(R / SYN_T), dim3(256), 0, s, (const __bf16*)st->ws_q, (const __bf16*)st->ws_k,
-                           (const __bf16*)st->ws_vt, (__bf16*)st->ws_o, R / SYN_T);
-        mark(ST_ATTN);
-        // proj + residual, LN2 -> xn
-        memset(&a, 0, sizeof(a));
-        a.X = (const __bf16*)st->ws_o; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_proj; a.K = SYN_D; a.M = R;
-        a.bias = L.b_proj; a.H = st->ws_h; a.Y = (__bf16*)st->ws_xn; a.ldy = SYN_D; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b;
-        if ((rc = launch_gemm<EPI_RESID>(a, mt, 1, s))) return rc;
-        mark(ST_PROJ);
-        // fc1 + gelu
-        memset(&a, 0, sizeof(a));
-        a.X = (const __bf16*)st->ws_xn; a.ldx = SYN_D; a.x_rows = R; a.W = (const uint4*)L.w_fc1; a.K = SYN_D; a.M = R;
-        a.bias = L.b_fc1; a.Y = (__bf16*)st->ws_hid; a.ldy = SYN_FF;
-        if ((rc = launch_gemm<EPI_GELU>(a, mt, 2, s))) return rc;
-        mark(ST_FC1);
-        // fc2 + residual, next block's LN1 -> xn (last block: plain bf16 copy, there is no final norm)
-        memset(&a, 0, sizeof(a));
-        a.X = (const __bf16*)st->ws_hid; a.ldx = SYN_FF; a.x_rows = R; a.W = (const uint4*)L.w_fc2; a.K = SYN_FF; a.M = R;
-        a.bias = L.b_fc2; a.H = st->ws_h; a.Y = (__bf16*)st->ws_xn; a.ldy = SYN_D;
-        if (l + 1 < SYN_LAYERS) { a.ln_g = md->layer[l + 1].ln1_g; a.ln_b = md->layer[l + 1].ln1_b; }
-        if ((rc = launch_gemm<EPI_RESID>(a, mt, 1, s))) return rc;
-        mark(ST_FC2);
-    }
-
-    // output stage (+ guidance combination of the variants, linear so it commutes with the GEMM)
-    if (!fuse_out) {
-        if (V > 1) {
-            const size_t n4 = (size_t)3 * Mb * kNT / 4;
-            hipLaunchKernelGGL(k_combine, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, st->ws_h, st->cfg_w, st->cfg_w_clip_stride, V, Mb,
-                               (__bf16*)st->ws_hc);
-            mark(ST_COMBINE);
-            aout.X = (const __bf16*)st->ws_hc; aout.x_chunk_stride = (long)Mb * kNT;
-        } else {
-            aout.X = (const __bf16*)st->ws_xn;
-        }
-        if ((rc = launch_gemm<EPI_OUT>(aout, st->m_tile ? st->m_tile : pick_tile(Mb), 3, s))) return rc;
-        mark(ST_OUT);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("syn_denoise_step", e);
+    return fail_msg(p.error);
 }
 
 int syn_denoise_step(const syn_model* md, const syn_step* st, void* stream) {

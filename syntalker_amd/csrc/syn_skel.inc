@@ -196,8 +196,7 @@ static int pack_weight(const float* w, const float* mask, const float* ws, const
     const int cout_p = (int)round_up(cout, kTile);
     hipLaunchKernelGGL(k_skel_pack, dim3((unsigned)(2 * cout_p / kTile)), dim3(64), 0, (hipStream_t)stream, w, mask, ws, ms, (int)cout, (int)cin,
                        cout_p, chunk_off, chunk_k, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_skel_pack launch", e);
+    return launched("k_skel_pack launch");
 }
 
 static int encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
@@ -232,13 +231,11 @@ static int encode(const syn_skel_model* m, const float* x, int32_t n_clips, int3
         const dim3 grid((unsigned)((long)n_clips * a.tiles));
         if (l == 0) hipLaunchKernelGGL(k_skel_conv<true>, grid, dim3(256), lds, st, a);
         else        hipLaunchKernelGGL(k_skel_conv<false>, grid, dim3(256), lds, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail("k_skel_conv launch", e);
+        if (int rc = launched("k_skel_conv launch")) return rc;
         src.y = a.y; src.st = a.st; src.gn_g = y.gn_g; src.gn_b = y.gn_b; src.pool_src = y.pool_src; src.pool_w = y.pool_w;
         src.cout = a.cout; src.cout_p = a.cout_p; src.t = a.t_out; src.tiles = a.tiles; src.width = y.out_width;
     }
     hipLaunchKernelGGL(k_skel_out, dim3((unsigned)((long)n_clips * src.tiles)), dim3(256), 0, st, src, src.tiles, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_skel_out launch", e);
+    return launched("k_skel_out launch");
 }
 }  // namespace skel

@@ -265,8 +265,7 @@ static int pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, i
     const long frags = layout == 0 ? round_up(n, kBN) / 16 * kq : (long)3 * layout / 16 * kq;
     hipLaunchKernelGGL(k_t2m_pack, dim3((unsigned)((frags * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, (int)conv_cin,
                        (int)layout, frags, kq, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_t2m_pack launch", e);
+    return launched("k_t2m_pack launch");
 }
 
 static int gemm(hipStream_t st, int amode, GemmArgs g) {
@@ -275,8 +274,7 @@ static int gemm(hipStream_t st, int amode, GemmArgs g) {
     if (amode == A_CONV)     hipLaunchKernelGGL(k_t2m_gemm<A_CONV>, grid, dim3(256), 0, st, g);
     else if (amode == A_LN)  hipLaunchKernelGGL(k_t2m_gemm<A_LN>, grid, dim3(256), 0, st, g);
     else                     hipLaunchKernelGGL(k_t2m_gemm<A_PLAIN>, grid, dim3(256), 0, st, g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("k_t2m_gemm launch", e);
+    return launched("k_t2m_gemm launch");
 }
 
 static int linear(hipStream_t st, const float* a, long lda, long m, int k, int n, const float* w, const float* bias, int epi, float* c, long ldc,
@@ -322,8 +320,7 @@ static int recur_and_head(hipStream_t st, const syn_t2m_gru& r, const syn_t2m_he
     static OncePerDevice once;                                 // > 64 KB of dynamic LDS needs the opt-in (H = 1024: 64.25 KB)
     if (once.first()) allow_lds(k_t2m_gru<H>, (int)lds);
     hipLaunchKernelGGL(k_t2m_gru<H>, dim3((unsigned)((n_seq + kRows - 1) / kRows), 2), dim3(64 * kGruWaves), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("k_t2m_gru launch", e);
+    if (int rc = launched("k_t2m_gru launch")) return rc;
     if (int rc = linear(st, hcat, 2 * H, n_seq, 2 * H, H, hd.w1, hd.b1, E_BIAS, y1, H)) return rc;
     GemmArgs g = {};
     g.a = y1; g.lda = H; g.m = n_seq; g.k = H; g.n = SYN_T2M_EMB; g.ln_g = hd.ln_g; g.ln_b = hd.ln_b; g.w = hd.w2; g.bias = hd.b2; g.epi = E_BIAS;

@@ -46,11 +46,6 @@ __device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
-static int launched(const char* what) {                        // after a launch of this file or syn_bert.inc
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(what, e);
-}
-
 // 256 threads; wave w owns output columns [64 w, 64 w + 64) of the tile, all 64 rows: acc[m tile][n tile].
 template <int EPI>
 __global__ __launch_bounds__(256) void k_tmr_gemm(const GemmArgs a) {

@@ -174,8 +174,10 @@ class StepBuffers:
         self.sync = torch.zeros(320, dtype=torch.int32, device=device)   # small-batch path: barrier counters + error flag
         s = _lib.SynStep()
         s.n_clips, s.n_variants, s.m_tile = B, V, m_tile
-        # 0 auto (small-batch kernel for few sequences, whole-step kernel otherwise); 4 / 3 / 5 pin one of them;
-        # 1 = five kernels per block (the restatement the whole-step kernel is checked against bit for bit)
+        # 0 auto, by plan_step (csrc/syn_step_plan.inc): the small-batch kernel while an XCD holds at most 4 sequences, unless the whole-step
+        # kernel's split tiles apply at 9..128 sequences (with the buffers below: small-batch up to 8 sequences, split tiles to 128, whole
+        # tiles beyond); 4 / 3 / 5 pin one of the kernels; 1 = five kernels per block (the restatement the whole-step kernel is checked
+        # against bit for bit)
         s.reserved = layer_mode
         s.cond, s.t_model, s.cfg_w = self.cond.data_ptr(), self.t_model.data_ptr(), _lib.ptr(self.cfg_w)
         s.x_t, s.x_t_bf16, s.noise = self.x.data_ptr(), self.xb.data_ptr(), self.noise.data_ptr()

@@ -380,6 +380,59 @@ def test_tile_split_over_workgroups_equals_one_workgroup_per_tile(beatx, B, V):
         assert rel_l2(outs[0][:n], want) < FWD_TOL
 
 
+def _filled_step_buffers(B, V, mode, seed=23):
+    """StepBuffers for one deterministic step (identity coefficients, no noise) on seeded random inputs."""
+    from syntalker_amd import engine
+    g = torch.Generator().manual_seed(seed)
+    sb = engine.StepBuffers(B, V, DEV, layer_mode=mode)
+    sb.cond.copy_(torch.randn(V * B * 32, 512, generator=g) * 0.5)
+    sb.load_x(torch.randn(B, 1536, 1, 32, generator=g).to(DEV))
+    sb.t_model.copy_((torch.arange(V * B, dtype=torch.int32) * 37) % 1000); sb.t_coef.zero_()
+    if V > 1:
+        sb.cfg_w.copy_(torch.tensor([[-1.5, 2.5]] * 3, device=DEV))
+    return sb
+
+
+@pytest.mark.parametrize("B,V,mode,want", [
+    (2, 1, 0, [0, 0, 0, 0, 0, 1, 0, 0]),         # small-batch kernel
+    (2, 1, 4, [0, 0, 0, 0, 0, 1, 0, 0]),         # whole-step kernel, output stage inside
+    (2, 1, 1, [1, 8, 8, 8, 8, 8, 0, 1]),         # per-operation path
+    (2, 2, 0, [0, 0, 0, 0, 0, 1, 0, 1]),         # small-batch kernel, sequences dealt to the XCDs + k_guided_update
+    (2, 2, 4, [0, 0, 0, 0, 0, 1, 1, 1]),         # whole-step kernel + k_combine + output GEMM
+    (2, 2, 1, [1, 8, 8, 8, 8, 8, 1, 1]),
+    (4, 1, 5, [0, 0, 0, 0, 0, 1, 0, 0]),         # wave-per-sequence kernel (fragment order)
+])
+def test_launch_structure_by_path(beatx, B, V, mode, want):
+    """What a step launches on each path, as syn_denoise_step_profile counts it: [IN, QKV, ATTN, PROJ, FC1, FC2, COMBINE, OUT]."""
+    import ctypes as C
+    from syntalker_amd import _lib, engine
+    pm = beatx.packed()
+    sb = _filled_step_buffers(B, V, mode)
+    ident = engine.identity_coefs(DEV)
+    sb.c.coef, sb.c.noise, sb.c.rng = ident.data_ptr(), None, None
+    ms, cnt = (C.c_float * 8)(), (C.c_int32 * 8)()
+    _lib.check(_lib.load().syn_denoise_step_profile(C.byref(pm.c), C.byref(sb.c), _lib.current_stream(pm.device), ms, cnt), "syn_denoise_step_profile")
+    assert torch.isfinite(sb.read(sb.x)).all()
+    assert list(cnt) == want
+
+
+@pytest.mark.parametrize("B,pin,xch", [(8, 3, True), (129, 4, True), (33, 4, False)],
+                         ids=["8-small-batch-kernel", "129-whole-tiles", "33-without-ws_xch-whole-tiles"])
+def test_automatic_choice_is_the_kernel_the_planner_names(beatx, B, pin, xch):
+    """reserved = 0 against the pin of the kernel the step planner names for that batch, bit for bit: the first sizes next to a planner
+    boundary that have a pin to compare with (8: last of the small-batch kernel before split tiles; 129: first past split tiles;
+    33 without ws_xch: first past the small-batch kernel where tiles cannot be split)."""
+    from syntalker_amd import engine
+    outs = []
+    for mode in (0, pin):
+        sb = _filled_step_buffers(B, 1, mode)
+        if not xch:
+            sb.c.ws_xch = None
+        engine.run_step(beatx.packed(), sb, engine.identity_coefs(DEV), False)
+        outs.append(sb.read(sb.x).cpu())
+    assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("B", [256, 1024], ids=["256-token-resident-kernel", "1024-wave-per-sequence-kernel"])
 def test_full_size_properties(beatx, B):
     """BASELINE-size batches (256 clips: k_stack; 1024 clips, the bench's batch: the library keeps the latent in fragment

@@ -300,6 +300,88 @@ def test_c_abi_entry_points_reject_null_and_zero_arguments_without_crashing():
     assert not accepted, accepted
 
 
+def test_step_planner_table():
+    """Which kernel runs a step, as a table: csrc/syn_step_plan.inc compiled on its own by g++ (tests/native/step_plan_host.cpp) and asked
+    every run of batch sizes on both sides of its boundaries.  256 CUs; answers are `LAT by_seq`, `STACK tile_rows tp fuse_out out_tile`,
+    `LAYERS tile_rows out_tile`, `SEQ`, or a substring of the error.  ws_x0v, where a row leaves it open, is present exactly when
+    V > 1 and B V <= 32, as engine.StepBuffers allocates it."""
+    import subprocess, tempfile
+    yes, no = (1,), (0,)
+    by_engine = None
+    whole32, whole64 = "STACK 32 1 1 0", "STACK 64 1 1 0"
+    # (V, reserved values, m_tile, ws_sync, ws_xch, ws_x0v, x_fragment_order, xcd8x32, [(first B, answer), ...])
+    rows = [
+        ((1,), (0,), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 0"), (9, "STACK 32 4 1 0"), (65, "STACK 32 2 1 0"), (129, whole32), (257, whole64)]),
+        ((1,), (0,), 0, yes, no, by_engine, 0, 1, [(1, "LAT 0"), (33, whole32), (257, whole64)]),
+        ((1,), (0,), 0, no, no, by_engine, 0, 1, [(1, whole32), (257, whole64)]),
+        ((1,), (0,), 0, yes, yes, by_engine, 0, 0, [(1, whole32), (257, whole64)]),
+        ((2,), (0,), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 1"), (5, "STACK 32 4 0 32"), (33, "STACK 32 2 0 32"), (65, "STACK 32 1 0 32"),
+                                                    (129, "STACK 64 1 0 32"), (257, "STACK 64 1 0 64")]),
+        ((2,), (0,), 0, yes, yes, no, 0, 1, [(1, "LAT 0"), (5, "STACK 32 4 0 32"), (33, "STACK 32 2 0 32"), (65, "STACK 32 1 0 32"),
+                                             (129, "STACK 64 1 0 32"), (257, "STACK 64 1 0 64")]),
+        ((3,), (0,), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 1"), (3, "STACK 32 4 0 32"), (22, "STACK 32 2 0 32"), (43, "STACK 32 1 0 32"),
+                                                    (86, "STACK 64 1 0 32"), (257, "STACK 64 1 0 64")]),
+        ((4,), (0,), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 1"), (3, "STACK 32 4 0 32"), (17, "STACK 32 2 0 32"), (33, "STACK 32 1 0 32"),
+                                                    (65, "STACK 64 1 0 32"), (257, "STACK 64 1 0 64")]),
+        ((1,), (4, 12), 0, yes, yes, by_engine, 0, 1, [(1, whole32), (257, whole64)]),                     # never LAT, never split
+        ((1,), (8,), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 0"), (33, whole32), (257, whole64)]),
+        ((1,), (3, 7), 0, yes, yes, by_engine, 0, 1, [(1, "LAT 0")]),                                     # at every B
+        ((1,), (3,), 0, no, (0, 1), by_engine, 0, 1, [(1, "ERROR syn_denoise_step: the latency path needs ws_sync")]),
+        ((1,), (1,), 0, (0, 1), (0, 1), by_engine, 0, 1, [(1, "LAYERS 32 32"), (257, "LAYERS 64 64")]),
+        ((1,), (1,), 128, (0, 1), (0, 1), by_engine, 0, 1, [(1, "LAYERS 128 128")]),
+        ((1,), (4,), 128, (0, 1), (0, 1), by_engine, 0, 1, [(1, whole64)]),                               # the whole-step kernel caps its tile at 64
+        ((1,), (0,), 64, yes, yes, by_engine, 0, 1, [(1, "LAT 0"), (33, whole64)]),       # a pinned tile switches split tiles off, not the small-batch kernel
+        ((1,), (2, 6), 0, (0, 1), (0, 1), by_engine, 0, 1, [(1, "ERROR syn_denoise_step: kernel selection 2 (two kernels per block) was removed in ABI 8")]),
+        ((1,), (5, 13), 0, (0, 1), (0, 1), by_engine, 0, 1, [(1, "ERROR syn_denoise_step: the wave-per-sequence kernel needs the latent in fragment order")]),
+        ((1, 2, 3, 4), tuple(range(16)), 0, (0, 1), (0, 1), by_engine, 1, 1, [(1, "SEQ")]),
+        ((5,), tuple(range(16)), 0, (0, 1), (0, 1), by_engine, 1, 1, [(1, "ERROR syn_denoise_step: fragment-order latents take at most 4 variants")]),
+    ]
+    queries, expected = [], []
+    for vs, reserved, m_tile, syncs, xchs, x0v, xfo, xcd, runs in rows:
+        for i, (first, answer) in enumerate(runs):
+            last = runs[i + 1][0] - 1 if i + 1 < len(runs) else 4096
+            for b in sorted({first, (first + last) // 2, last}):               # both sides of every boundary, and the last run far out
+                for v in vs:
+                    for r in reserved:
+                        for sy in syncs:
+                            for xc in xchs:
+                                has_x0v = int(v > 1 and b * v <= 32) if x0v is by_engine else x0v[0]
+                                queries.append(f"plan {b} {v} {r} {m_tile} {sy} {xc} {has_x0v} {xfo} 256 {xcd}")
+                                expected.append(answer)
+    grids = {(1024, 1): 256, (5, 2): 3, (5, 3): 5, (5, 4): 5}
+    queries += [f"grid {b} {v}" for b, v in grids]
+    expected += [str(g) for g in grids.values()]
+    with tempfile.TemporaryDirectory() as td:
+        exe = os.path.join(td, "step_plan_host")
+        subprocess.run(["g++", "-std=c++17", "-I", os.path.join(REPO, "syntalker_amd", "csrc"), os.path.join(REPO, "tests", "native", "step_plan_host.cpp"),
+                        "-o", exe], check=True)
+        out = subprocess.run([exe], input="\n".join(queries) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(queries)
+    wrong = [(q, got, want) for q, got, want in zip(queries, out, expected) if not (got.startswith(want) if want.startswith("ERROR") else got == want)]
+    assert not wrong, wrong[:10]
+
+
+def test_prefers_fragment_order_follows_the_pass_counts():
+    """syn_prefers_fragment_order through the built library (256 CUs assumed without a device): k_seq is preferred where its passes over the
+    CUs, at 1.91 times k_stack's per pass, come to less than k_stack's - whole blocks of batch sizes."""
+    from syntalker_amd import _lib
+    lib = _lib.load()
+    sizes = range(1, 4225)
+
+    def on(v):
+        return {b for b in sizes if lib.syn_prefers_fragment_order(b, v)}
+
+    def blocks(first, length, period, end=4096):
+        return {b for lo in range(first, end, period) for b in range(lo, lo + length)}
+
+    assert on(1) == blocks(513, 512, 1024)                # 513..1024, 1537..2048, 2561..3072, 3585..4096
+    assert on(2) == blocks(257, 256, 512)                 # 257..512, 769..1024, ..., 3841..4096
+    # V = 4, one clip per workgroup: 129..256, 385..512, ... with period 256; in the other halves k_seq's k + 1 passes meet 2 k + 1 of k_stack,
+    # and 191 (k + 1) < 100 (2 k + 1) from k = 11 on, so from 2817 clips every size prefers it
+    assert on(4) == blocks(129, 128, 256, end=4224) | set(range(2817, 4225))
+    assert not on(0) and not on(3) and not on(5)
+
+
 def test_dropin_aliases_resolve():
     from syntalker_amd import dropin
     dropin.install()
