@@ -15,13 +15,13 @@ fi
 grep -v "remark:" "$LOG" >&2 || true
 # k_seq lives within a few registers of the 512 a wave has: an edit that tips hipcc's allocator over shows up
 # as hundreds of spilled registers and a 20-30 % slower step, not as an error.  Say so at build time.
-# (six instances: plain / guided batches x the noise term of the update - none, read, drawn in the epilogue)
+# (six instances, in the order hipcc reports them: plain / guided batches x the noise term of the update - drawn in the epilogue, read, none)
 spills=$(grep -A12 "Function Name: .*k_seq" "$LOG" | grep "VGPRs Spill" | sed 's/.*VGPRs Spill: \([0-9]*\).*/\1/' | tr '\n' ' ' || true)
 rm -f "$LOG"
-echo "k_seq: ${spills:-?}spilled VGPRs (instances: {plain, guided} x noise {none, read, drawn})"
+echo "k_seq: ${spills:-?}spilled VGPRs (instances: {plain, guided} x noise {drawn, read, none})"
 for n in ${spills}; do
     if [ "${n}" -gt 80 ]; then
-        echo "WARNING: k_seq spills ${n} VGPRs (normal: 47 - 62 around the step loop, 18 - 22 for the guided instances, none inside the block loops): the register allocation tipped over, expect a much slower step" >&2
+        echo "WARNING: k_seq spills ${n} VGPRs (normal: 19 - 26 around the step loop, 18 - 22 for the guided instances, none inside the input, head and MLP loops): the register allocation tipped over, expect a much slower step" >&2
     fi
 done
 echo "built $(pwd)/libsyn_hip.so"

@@ -413,20 +413,33 @@ __device__ __forceinline__ f32x4 plain_residual(const GArgs& a, f32x4 v, int m, 
 }
 
 
+// a ^ b ^ c as ONE instruction: gfx950 has no v_xor3_b32, but v_bitop3_b32 evaluates any three-input truth table (0x96: odd parity),
+// and hipcc does not form it from the expression (two v_xor_b32).  The generator runs in the shadow of MFMAs, where every vector
+// instruction counts: 20 instead of 39 logic operations per four normals.
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+    if (__builtin_constant_p(b) && b == 0) return a ^ c;            // (the high counter words of round 0 are usually constant zeros)
+    return (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+}
 // Philox4x32-10 (Salmon et al. 2011), counter = (index/4, stream_id), key = seed; Box-Muller pairs.
+// X3 = false: the two-xor form of the same round (same bits).  k_seq's guided drawn-noise instance takes it: with the one-instruction
+// form hipcc's register allocation of that instance tips over (41 spilled registers against 18, 14 scratch accesses inside its output
+// pair loop against 2).
+template <bool X3 = true>
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
+    const uint32_t n0 = X3 ? xor3((uint32_t)(p1 >> 32), c[1], k[0]) : (uint32_t)(p1 >> 32) ^ c[1] ^ k[0];
+    const uint32_t n2 = X3 ? xor3((uint32_t)(p0 >> 32), c[3], k[1]) : (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
     c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
     k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
 }
 
 // Four N(0,1) values for elements [4*idx4, 4*idx4+3] of the flat noise tensor of step `stream_id`.
+template <bool X3 = true>
 __device__ __forceinline__ f32x4 randn4(uint64_t seed, uint64_t stream_id, uint64_t idx4) {
     uint32_t c[4] = {(uint32_t)idx4, (uint32_t)(idx4 >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
     uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma unroll
-    for (int r = 0; r < 10; ++r) philox_round(c, k);
+    for (int r = 0; r < 10; ++r) philox_round<X3>(c, k);
     const float inv32 = 2.3283064365386963e-10f;   // 2^-32
     f32x4 z;
 #pragma unroll

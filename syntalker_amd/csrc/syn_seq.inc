@@ -741,8 +741,11 @@ __global__ __launch_bounds__(kThreads) void k_seq(const QArgs) {
         // adds: ~110 vector instructions per 4 channels of 32 tokens) is issued one quad per 4 k-chunks in the shadow of pair p's
         // MFMAs, its x_t was requested one pair earlier, its stores go out as they are produced.
         // (defined before the pair loop: left undefined, hipcc carries their registers around the whole step loop - 40 spilled)
-        f32x16 pacc[2] = {zero16(), zero16()};
-        f32x4 pxt[2][4], xo;
+        // Two sets of accumulators and x_t registers, taken in turn: the update of pair p-1 reads the set that pair p does not
+        // write, so nothing is copied between pairs (one set handed on to a "previous pair" copy cost 64 v_accvgpr_mov and 32 v_mov
+        // per pair).  The odd pairs' set is carried around the loop (and read after it), so it is the one defined here.
+        f32x16 acc_odd[2] = {zero16(), zero16()};
+        f32x4 xt_odd[2][4], xo;
         // G: this wave's two 8 KB exchange buffers (its slab), and the slabs of its clip's variants
         [[maybe_unused]] const int nvar = G ? a->V : 1;
         [[maybe_unused]] unsigned gat = (unsigned)(kSlabBase + group0 * kSlabBytes + lane * 16);
@@ -751,7 +754,7 @@ __global__ __launch_bounds__(kThreads) void k_seq(const QArgs) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) pxt[u][q] = xo;
+            for (int q = 0; q < 4; ++q) xt_odd[u][q] = xo;
         auto fetch = [&](int off, f32x4 (&xt)[2][4]) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -759,8 +762,9 @@ __global__ __launch_bounds__(kThreads) void k_seq(const QArgs) {
                 for (int q = 0; q < 4; ++q)
                     xt[u][q] = (SEQ_ABL & 16) ? f32x4{1.f, 2.f, 3.f, 4.f} : *reinterpret_cast<const f32x4*>(xt_s + off + (u * 4 + q) * 1024);
         };
-        // channels 32 nf + 8 q + 4 hi .. + 3 of the pair whose offsets are off_f / off_b; pr: that pair's index (G only)
-        auto quad = [&](int pr, int u, int q) {
+        // channels 32 nf + 8 q + 4 hi .. + 3 of the pair whose offsets are off_f / off_b; pr: that pair's index (G only);
+        // pacc / pxt: that pair's accumulators and x_t
+        auto quad = [&](int pr, int u, int q, const f32x16 (&pacc)[2], const f32x4 (&pxt)[2][4]) {
             const int at_f = off_f + (u * 4 + q) * 1024;
             f32x4 x0;
             if constexpr (!G) {
@@ -777,7 +781,7 @@ __global__ __launch_bounds__(kThreads) void k_seq(const QArgs) {
             f32x4 xv;
             [[maybe_unused]] f32x4 z;
             if constexpr (NZ == 1) z = *reinterpret_cast<const f32x4*>(nz_s + at_f);
-            if constexpr (NZ == 2) z = randn4(seed, (uint64_t)tc, idx4 + (unsigned long long)(8 * u + 2 * q));
+            if constexpr (NZ == 2) z = randn4<!G>(seed, (uint64_t)tc, idx4 + (unsigned long long)(8 * u + 2 * q));
 #pragma unroll
             for (int e = 0; e < 4; ++e) {                            // (element by element: see nopk)
                 float v = fmaf(x0[e], cf[0], nopk(pxt[u][q][e] * cf[1]));
@@ -800,41 +804,60 @@ __global__ __launch_bounds__(kThreads) void k_seq(const QArgs) {
             off_f += 8192; off_b += 4096;
             if constexpr (NZ == 2) idx4 += 16;
         };
+        if constexpr (!G) {
+            // pair pr into acc / cxt, the update of pair pr - 1 out of pacc / pxt
+            auto pair = [&](int pr, bool first, f32x16 (&acc)[2], f32x4 (&cxt)[2][4], const f32x16 (&pacc)[2], const f32x4 (&pxt)[2][4]) {
+                acc[0] = bias_tile(lds, SYN_LAYERS, 0, 2 * pr, hi); acc[1] = bias_tile(lds, SYN_LAYERS, 0, 2 * pr + 1, hi);
+                fetch(first ? off_f : off_f + 8192, cxt);            // consumed during the NEXT pair's MFMAs
+                if (first) {
+                    pair512<false>(r, lds, hb, acc[0], acc[1]);
+                } else {
+                    pair512<false>(r, lds, hb, acc[0], acc[1], [&](int kc) {
+                        if ((kc & 3) == 0) quad(pr - 1, kc >> 4, (kc >> 2) & 3, pacc, pxt);
+                    });
+                    advance();
+                }
+            };
 #pragma unroll 1
-        for (int pr = 0; pr < 24; ++pr) {
-            f32x16 acc0 = bias_tile(lds, SYN_LAYERS, 0, 2 * pr, hi), acc1 = bias_tile(lds, SYN_LAYERS, 0, 2 * pr + 1, hi);
-            f32x4 cxt[2][4];
-            fetch(pr == 0 ? off_f : off_f + 8192, cxt);              // consumed during the NEXT pair's MFMAs
-            if (pr == 0) {
-                pair512<false>(r, lds, hb, acc0, acc1);
-            } else {
-                pair512<false>(r, lds, hb, acc0, acc1, [&](int kc) {
-                    if ((kc & 3) == 0) {
-                        if constexpr (!G) quad(pr - 1, kc >> 4, (kc >> 2) & 3);
-                        else if (((kc >> 3) % nvar) == var) quad(pr - 1, kc >> 4, (kc >> 2) & 3);     // quad pair kc >> 3 is this wave's
-                    }
-                });
-                advance();
+            for (int pp = 0; pp < 12; ++pp) {
+                f32x16 acc_even[2];
+                f32x4 xt_even[2][4];
+                pair(2 * pp, pp == 0, acc_even, xt_even, acc_odd, xt_odd);
+                pair(2 * pp + 1, false, acc_odd, xt_odd, acc_even, xt_even);
             }
-            if constexpr (!G) {
-                pacc[0] = acc0; pacc[1] = acc1;
-            } else {
+        } else {
+            // The variants' tiles pass through the LDS; all that is handed from pair to pair in registers is x_t (32 moves), and the
+            // two-set form of the loop tips the guided instances' register allocation over (46 spilled registers against 22): one
+            // pair per iteration, x_t handed on through xt_odd.
+#pragma unroll 1
+            for (int pr = 0; pr < 24; ++pr) {
+                f32x16 acc0 = bias_tile(lds, SYN_LAYERS, 0, 2 * pr, hi), acc1 = bias_tile(lds, SYN_LAYERS, 0, 2 * pr + 1, hi);
+                f32x4 cxt[2][4];
+                fetch(pr == 0 ? off_f : off_f + 8192, cxt);          // consumed during the NEXT pair's MFMAs
+                if (pr == 0) {
+                    pair512<false>(r, lds, hb, acc0, acc1);
+                } else {
+                    pair512<false>(r, lds, hb, acc0, acc1, [&](int kc) {
+                        if ((kc & 3) == 0 && ((kc >> 3) % nvar) == var) quad(pr - 1, kc >> 4, (kc >> 2) & 3, acc_odd, xt_odd);   // quad pair kc >> 3 is this wave's
+                    });
+                    advance();
+                }
                 // publish: the chunk barrier that opens the next pair (or the one below, after the last) makes it everybody's;
                 // the buffer written now was last read during pair pr - 1, i.e. before every wave's latest barrier
                 char* const mine = slab + (pr & 1) * 8192;
                 slab_store(mine, 0, acc0);
                 slab_store(mine, 1, acc1);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) xt_odd[u][q] = cxt[u][q];
             }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) pxt[u][q] = cxt[u][q];
         }
         if constexpr (G) __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int i = 0; i < 8; ++i)                                  // the last pair's update has nobody to hide behind
-            if (!G || ((i >> 1) % nvar) == var) quad(23, i >> 2, i & 3);
+            if (!G || ((i >> 1) % nvar) == var) quad(23, i >> 2, i & 3, acc_odd, xt_odd);
     }
     if (stamp) a->dbg[(size_t)blockIdx.x * 32 + 10] = (long long)__builtin_readcyclecounter();
   }
