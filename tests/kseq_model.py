@@ -17,6 +17,28 @@ def bf16(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).float().numpy()
 
 
+def _fma32(a, b, c):
+    """fmaf on float32 arrays: the product of two floats is exact in a double, one rounding of the sum to double, one to float."""
+    return (a.astype(np.float64) * np.asarray(b, np.float64) + np.float64(c)).astype(np.float32)
+
+
+GELU_X2_CLAMP = np.float32(64.0)
+
+
+def gelu_kseq(x, clamp=GELU_X2_CLAMP):
+    """`gelu_fast` of syn_seq.inc in float32, same constants and operation order: x * rcp(1 + exp2(x * t(min(x^2, 64)))).
+    clamp=None is the formula without its clamp (what the kernel ran before it had one): the tests show that they tell the two apart."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        x2 = x * x
+        if clamp is not None:
+            x2 = np.fmin(x2, clamp)                                   # v_min_f32: a NaN x^2 becomes the clamp, x itself carries the NaN on
+        t = _fma32(np.float32(1.0142633e-3), x2, np.float32(-1.0677573e-1))
+        t = _fma32(t, x2, np.float32(-2.3011213))
+        e = np.exp2(x * t)
+        return x * (np.float32(1.0) / (np.float32(1.0) + e))
+
+
 def mfma32(a, b, c):
     """D = A.B + C for v_mfma_f32_32x32x16_bf16.  a, b: [64][8] (bf16 values as fp32), c: [64][16] fp32.
     A[i][k]: lane = 32*(k//8) + i, slot k%8.  B[k][j]: lane = 32*(k//8) + j, slot k%8.
