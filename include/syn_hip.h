@@ -818,6 +818,58 @@ int syn_vq_quantize(const float* x, const float* codebooks, const float* codeboo
 /* Sum of the codes of given indices (RVQVAE.forward_decoder, models/vq/model.py:86-89): idx [rows][n_q], -1 = no code. */
 int syn_vq_codes(const int32_t* idx, const float* codebooks, float* q_f32, void* q_bf16, int32_t rows, int32_t n_q, void* stream);
 
+/* ---- RVQ-VAE training (reference rvq_beatx_train.py over models/vq/ in train mode; additive, ABI 9) ----------
+ * The step's convolutions - forward and data gradients - are syn_vq_conv1d calls; these are the pieces around them.  No entry point
+ * allocates, synchronises or uses a floating-point atomic: a step is bitwise reproducible.
+ * syn_vq_train_pack: n_jobs packing jobs in ONE launch, read from device memory: an array of
+ *   { const float* w; void* out; int32_t cout, cin, taps, cout_p, cin_p, kind; }   (40 bytes)
+ * kind 0: Conv1d weight fp32 [cout][cin][taps] -> syn_vq_conv.w_packed fragments for (cout_p, cin_p); kind 1: the data gradient's operand
+ * W'[ci][co][taps-1-tap] = W[co][ci][tap], fragments for (cout_p = pad128(cin), cin_p = pad32(cout)); kind 2: fp32 vector [cout] -> [cout_p], zero
+ * padded; kind 3: as kind 0 of bf16(w - float(bf16(w))), the part of the weight its bf16 copy drops.  max_units = the largest job's taps * cout_p/16 * cin_p/32 * 64 (kind 2: cout_p). */
+int syn_vq_train_pack(const void* jobs_dev, int32_t n_jobs, int32_t max_units, void* stream);
+/* x fp32 [rows][dim] -> bf16 [rows][dim_padded], zero padded (the first convolution's operand); out_lo_bf16 (NULL to skip) = bf16(x - float(bf16(x))) */
+int syn_vq_train_cast(const float* x, int64_t rows, int32_t dim, int32_t dim_padded, void* out_bf16, void* out_lo_bf16, void* stream);
+/* out = scale_resid * resid + scale_v * [relu_src > 0] * [keep != 0] * v over n (% 4 == 0) elements; resid, relu_src_bf16, keep (bytes) optional,
+ * out_f32 / out_bf16 / out_lo_bf16: at least one.  out_lo_bf16 = bf16(out - float(bf16(out))), stored as zero where out <= 0 when lo_relu != 0 (for a
+ * consumer that applies ReLU by the sign of the high part).  Dropout + residual add behind conv2 (resnet.py:66-67), the high / low split of the
+ * training forward's activations, the ReLU masks of the backward, the encoder's gradient. */
+int syn_vq_train_ew(const float* v, const float* resid, const void* relu_src_bf16, const uint8_t* keep, float scale_v, float scale_resid,
+                    float* out_f32, void* out_bf16, void* out_lo_bf16, int32_t lo_relu, int64_t n, void* stream);
+/* backward of nn.Upsample(2, nearest): out [rows_out][channels] = du[2 r] + du[2 r + 1] */
+int syn_vq_train_pairsum(const float* du, float* out, int64_t rows_out, int32_t channels, void* stream);
+/* out bf16 [2 rows_in][channels]: out[2 r] = dy[r], out[2 r + 1] = 0 - the stride-2 convolutions' data gradient as a stride-1 convolution */
+int syn_vq_train_stuff(const void* dy_bf16, void* out_bf16, int64_t rows_in, int32_t channels, void* stream);
+/* dw fp32 [cout][cin][taps] = sum_{n,t} dy[n][t][co] * x[n][(t*stride + tap*dil - pad) >> up][ci] (ReLU on x when relu_in), db [cout] = sum dy (NULL to
+ * skip); dy bf16 [clips][t_out][ldy], x bf16 [clips][t_in][ldx].  bf16 MFMA, fp32 accumulation, one workgroup sums all positions of its tile in
+ * order.  Reads outside a clip's frames are bounds-checked to zero. */
+int syn_vq_train_wgrad(const void* dy_bf16, int32_t ldy, const void* x_bf16, int32_t ldx, float* dw, float* db, int32_t clips, int32_t t_in,
+                       int32_t t_out, int32_t cout, int32_t cin, int32_t taps, int32_t stride, int32_t dil, int32_t pad, int32_t up, int32_t relu_in,
+                       void* stream);
+/* one layer's codebook fp32 [512][512] -> its transpose and |code|^2 [512] (what syn_vq_quantize / syn_vq_train_quantize take) */
+int syn_vq_train_codebook_prep(const float* codebook, float* codebook_t, float* code_sq, void* stream);
+/* init_codebook (quantizer.py:60-65): codebook = code_sum = _tile(x)[:512], code_count = 1; x fp32 [rows][512], noise fp32 [512][512] normal draws
+ * (required when rows < 512: row c = x[c % rows] + noise[c] * 0.01 / sqrt(512)) */
+int syn_vq_train_tile(const float* x, int32_t rows, const float* noise, float* codebook, float* code_sum, float* code_count, void* stream);
+/* One layer of ResidualVQ.forward in training, without the codebook update: index = argmax(-distance / temperature + gumbel) (gumbel fp32
+ * [rows][512], NULL: plain argmin), idx [rows][6] column `layer`; x_out = x_in - quantised (must not alias x_in); q_acc (+)= the straight-through
+ * output, q_bf16 (NULL to skip) = bf16(q_acc), resid_sum (+)= x_in - code; `first` != 0 starts both sums.  sqerr [syn_vq_quantize_groups(rows)]. */
+int syn_vq_train_quantize(const float* x_in, const float* codebook, const float* codebook_t, const float* code_sq, const float* gumbel, float temperature,
+                          float* x_out, float* q_acc, void* q_bf16, float* resid_sum, int32_t* idx, float* sqerr, int32_t layer, int32_t first, int32_t rows,
+                          void* stream);
+/* update_codebook (quantizer.py:107-130) of one layer from its input rows and indices: EMA of the per-code sums (rows added in ascending order) and
+ * counts, usage = count >= 1, unused codes <- _tile(x)[:512] (noise as in syn_vq_train_tile); batch_count fp32 [512] = this batch's counts. */
+int syn_vq_train_codebook_update(const float* x_in, const int32_t* idx, int32_t layer, int32_t rows, const float* noise, float mu, float one_minus_mu,
+                                 float* codebook, float* code_sum, float* code_count, float* batch_count, void* stream);
+/* Reconstruction loss over the real channels (kind 0: MSE, 1: L1, 2: SmoothL1 beta 1; mean over rows * dim): parts [syn_vq_train_loss_parts] =
+ * per-workgroup sums, d_rec_bf16 [rows][dim_padded] = d loss / d rec, zero in the padding. */
+int32_t syn_vq_train_loss_parts(int64_t rows, int32_t dim_padded);
+int syn_vq_train_loss(const float* rec, const float* gt, int64_t rows, int32_t dim, int32_t dim_padded, int32_t kind, void* d_rec_bf16, float* parts,
+                      void* stream);
+/* out4 = {loss, recons, commit, perplexity}: recons = sum(parts) / count, commit / perplexity = means over the n_active layers of
+ * sqerr[q][groups] / (rows * 512) and exp(-sum p log(p + 1e-7)), p = batch_count[q] / rows; loss = recons + commit_weight * commit. */
+int syn_vq_train_scalars(const float* parts, int32_t n_parts, int64_t count, const float* sqerr, int32_t groups, const float* batch_count, int32_t n_active,
+                         int32_t rows, float commit_weight, float* out4, void* stream);
+
 /* ---- training building block ------------------------------------------------------------------------
  * y[m][n] = sum_k x[m][k] * W[n][k] (+ bias[n]): nn.Linear forward on the MFMA GEMM (bf16 operands, fp32 accumulate
  * and output).  The same entry point serves the backward passes with re-packed operands:

@@ -27,7 +27,10 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
            "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
            "syn_tmr_pack_weight", "syn_tmr_encode", "syn_bert_encode", "syn_skel_pack_weight", "syn_skel_encode",
-           "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text")
+           "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text",
+           "syn_vq_train_pack", "syn_vq_train_cast", "syn_vq_train_ew", "syn_vq_train_pairsum", "syn_vq_train_stuff", "syn_vq_train_wgrad",
+           "syn_vq_train_codebook_prep", "syn_vq_train_tile", "syn_vq_train_quantize", "syn_vq_train_codebook_update",
+           "syn_vq_train_loss_parts", "syn_vq_train_loss", "syn_vq_train_scalars")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -122,6 +125,11 @@ class SynCondWeights(C.Structure):
 class SynVqConv(C.Structure):
     _fields_ = [("w_packed", vp), ("bias", vp), ("cin", i32), ("cout", i32), ("cout_valid", i32), ("taps", i32),
                 ("stride", i32), ("dil", i32), ("pad", i32), ("up", i32), ("relu_in", i32), ("relu_out", i32)]
+
+
+class SynVqTrainPackJob(C.Structure):
+    """include/syn_hip.h syn_vq_train_pack: one packing job, read by the kernel from device memory."""
+    _fields_ = [("w", vp), ("out", vp), ("cout", i32), ("cin", i32), ("taps", i32), ("cout_p", i32), ("cin_p", i32), ("kind", i32)]
 
 
 class SynVqModel(C.Structure):
@@ -324,6 +332,19 @@ def load():
     lib.syn_t2m_workspace_bytes.argtypes = [i32, i32, i32]
     lib.syn_t2m_encode_motion.argtypes = [C.POINTER(SynT2mModel), vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.syn_t2m_encode_text.argtypes = [C.POINTER(SynT2mModel), vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.syn_vq_train_pack.argtypes = [vp, i32, i32, vp]
+    lib.syn_vq_train_cast.argtypes = [vp, i64, i32, i32, vp, vp, vp]
+    lib.syn_vq_train_ew.argtypes = [vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, i64, vp]
+    lib.syn_vq_train_pairsum.argtypes = [vp, vp, i64, i32, vp]
+    lib.syn_vq_train_stuff.argtypes = [vp, vp, i64, i32, vp]
+    lib.syn_vq_train_wgrad.argtypes = [vp, i32, vp, i32, vp, vp] + [i32] * 11 + [vp]
+    lib.syn_vq_train_codebook_prep.argtypes = [vp, vp, vp, vp]
+    lib.syn_vq_train_tile.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.syn_vq_train_quantize.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.syn_vq_train_codebook_update.argtypes = [vp, vp, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp]
+    lib.syn_vq_train_loss_parts.argtypes = [i64, i32]
+    lib.syn_vq_train_loss.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp]
+    lib.syn_vq_train_scalars.argtypes = [vp, i32, i64, vp, i32, vp, i32, i32, f32, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes",

@@ -137,6 +137,20 @@ def synth_vq_rec_latent(sd: dict, part: str, n: int = 2, t: int = 16) -> torch.T
     return rec
 
 
+def synth_vq_motion(n: int, t: int, dim: int, step: int = 0, seed: int = 61) -> torch.Tensor:
+    """A batch (n, t, dim) of structured motion for codec-training runs: per channel a sum of three sinusoids whose frequencies and
+    amplitudes belong to the "dataset" (`seed`), per clip a start time and a gain drawn for batch number `step`."""
+    g = _gen("vq.motion.dataset", seed)
+    freq = 0.02 + 0.2 * torch.rand(3, dim, generator=g)                       # cycles per frame
+    amp = torch.rand(3, dim, generator=g) * torch.tensor([1.0, 0.5, 0.25]).view(3, 1)
+    phase = 6.283185307179586 * torch.rand(3, dim, generator=g)
+    gb = _gen(f"vq.motion.batch.{step}", seed)
+    t0 = 1000.0 * torch.rand(n, 1, 1, 1, generator=gb)
+    gain = 0.75 + 0.5 * torch.rand(n, 1, 1, generator=gb)
+    frames = torch.arange(t, dtype=torch.float32).view(1, t, 1, 1) + t0
+    return gain * (amp * torch.sin(6.283185307179586 * freq * frames + phase)).sum(dim=2)
+
+
 # ---- a long take for the chunked driver (diffusion_rvqvae_trainer.py:359-541): what `_load_data` hands `_g_test` ---------------
 def synth_long_take(n_pose: int, seed: int = 21) -> dict:
     """One take (batch 1, as the reference's test loader delivers it): axis-angle pose (1, n, 165), audio (1, n*533, 2),
