@@ -172,6 +172,25 @@ int syn_step_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, i
 int syn_steps_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, int32_t n_t_model, int32_t* t_coef,
                       int32_t n_t_coef, int32_t n_steps, void* stream);
 
+/* Pseudo linear multistep sampling (diffusion/gaussian_diffusion.py:1004-1086, orders 2-4).  A PLMS step is syn_denoise_step with a coefficient
+ * row that carries the Adams-Bashforth weight of the step's own noise estimate and noise = H, the weighted sum of the earlier estimates;
+ * syn_plms_update keeps that history.  One row of its table per launch of a loop: */
+typedef struct syn_plms_row {
+    float   r, inv_m;   /* e_new = (r * x_t - pred_x0) * inv_m: sqrt_recip_alphas_cumprod[t], 1 / sqrt_recipm1_alphas_cumprod[t]            */
+    float   h_x;        /* H = h_x * x_t + w_new * e_new + sum_k w[k] * ring[k]: what the NEXT step injects                                */
+    float   w_new;
+    float   w[3];       /* by ring slot; a slot with weight 0 is not read                                                                   */
+    int32_t store;      /* ring slot e_new overwrites, -1: e_new is not kept.  A row with store < 0 and every weight 0 does nothing          */
+} syn_plms_row;
+
+/* After a step that read x_t and wrote pred_x0 (x_next != x_t: the step must not have overwritten its input): row *counter - back of
+ * table [n_rows] (outside the table: nothing happens) -> e_new into ring [3][n], the next step's H into h [n].  Element-wise over n floats
+ * (a multiple of 4; every pointer 16-byte aligned), the same for token-major and fragment-order latents.  `counter` is the step counter
+ * syn_step_advance / syn_steps_advance maintain, `back` how many steps it is ahead of the step this call follows (1 after syn_step_advance;
+ * n_steps - s for step s of a syn_steps_advance row set).  Graph-capturable like everything else. */
+int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
+                    float* ring, float* h, int64_t n, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

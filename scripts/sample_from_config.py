@@ -4,11 +4,12 @@ YAML -> args namespace -> denoiser + diffusion + the three body-part RVQ-VAEs (+
 window-by-window sampling of whole takes -> RVQ-VAE decoding -> poses / root translation, all on the device -> optional
 Fréchet statistic of the sampled latents against reference statistics.
 
-    python scripts/sample_from_config.py configs.yaml [--seconds 8] [--takes 4] [--ddim] [--seed 1]
+    python scripts/sample_from_config.py configs.yaml [--seconds 8] [--takes 4] [--ddim] [--plms [--plms-order K]] [--seed 1]
                                          [--random-init] [--inputs in.npz] [--ref-stats ref.npz] [--out out.npz]
                                          [--upper-prompt TEXT] [--hands-prompt TEXT] [--lower-prompt TEXT]
                                          [--keep-from TAKE.npz [--keep-parts upper,hands,lower] [--keep-frames a:b]]
 
+--plms          the pseudo linear multistep sampler (`plms_sample_loop`) over the 50-step respacing, at order K = 2 (default), 3 or 4.
 --random-init   ignore the checkpoint / statistics paths of the YAML and use the name-keyed synthetic weights (there is no
                 network for the reference's checkpoints here); without it every configured path must exist.
 --inputs        npz with audio (B, n*533, 2), word (B, n), seed (B, n/4, 1536); default: synthetic inputs.
@@ -87,6 +88,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--takes", type=int, default=1)
     ap.add_argument("--ddim", action="store_true")
+    ap.add_argument("--plms", action="store_true")
+    ap.add_argument("--plms-order", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--random-init", action="store_true")
     ap.add_argument("--inputs")
@@ -124,7 +127,9 @@ def main(argv=None) -> dict:
     _, rounds, _ = longform.window_plan(n, pose_length, pre, squeeze)
     if rounds < 1:
         raise SystemExit(f"{n} pose frames are less than one window of {pose_length}")
-    diffusion = create_gaussian_diffusion(use_ddim=a.ddim)
+    if a.plms and a.ddim:
+        raise SystemExit("--plms and --ddim are two samplers: give one")
+    diffusion = create_gaussian_diffusion(use_ddim=a.ddim or a.plms)
     prompts = {part: getattr(a, f"{part}_prompt") for part in PROMPT_PARTS}
     model, y_extra, style_dim = s.model, None, 256 if config.is_h3d(args) else 512       # the h3d denoiser's style input is 256 wide
     if any(v is not None for v in prompts.values()):
@@ -136,13 +141,14 @@ def main(argv=None) -> dict:
     edit = edit_from_take(a, args, s, dev, n, word.shape[0], squeeze) if a.keep_from else None
     torch.cuda.synchronize(); t0 = time.perf_counter()
     lat = longform.sample_long(diffusion, model, audio, word, seed_lat, n, pose_length=pose_length, pre_frames=pre, squeeze=squeeze,
-                               use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra, edit=edit)
+                               use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra, edit=edit,
+                               **({"sampler": "plms", "plms_order": a.plms_order} if a.plms else {}))
     torch.cuda.synchronize(); t1 = time.perf_counter()
     out = longform.decode_take(lat, s.vq["upper"], s.vq["hands"], s.vq["lower"], s.latent_scale, use_trans=s.use_trans,
                                trans_mean=s.trans_mean, trans_std=s.trans_std)
     torch.cuda.synchronize(); t2 = time.perf_counter()
     rep = {"config": a.config, "pose_frames": int(n), "windows": int(rounds), "takes": int(word.shape[0]),
-           "sampler": "ddim50" if a.ddim else "ddpm1000", "sampling_s": round(t1 - t0, 4), "decoding_s": round(t2 - t1, 4),
+           "sampler": f"plms50-order{a.plms_order}" if a.plms else "ddim50" if a.ddim else "ddpm1000", "sampling_s": round(t1 - t0, 4), "decoding_s": round(t2 - t1, 4),
            "latents": list(lat.shape), "poses": {k: (None if v is None else list(v.shape)) for k, v in out.items()},
            "prompts": {k: v for k, v in prompts.items() if v is not None},
            "finite": bool(all(v is None or bool(torch.isfinite(v).all()) for v in out.values()))}

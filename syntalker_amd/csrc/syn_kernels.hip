@@ -1751,6 +1751,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_bert.inc"
 #include "syn_skel.inc"
 #include "syn_t2m.inc"
+#include "syn_plms.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2244,6 +2245,11 @@ int syn_steps_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, 
 int syn_step_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, int32_t n_t_model, int32_t* t_coef, int32_t n_t_coef,
                      void* stream) {
     return syn_steps_advance(sched, counter, t_model, n_t_model, t_coef, n_t_coef, 1, stream);
+}
+
+int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
+                    float* ring, float* h, int64_t n, void* stream) {
+    return plms::update(table, n_rows, counter, back, x_t, pred_x0, ring, h, n, stream);
 }
 
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {

@@ -177,17 +177,17 @@ class MDM(nn.Module):
             self._syn_cond_entry = None
         return self._syn_packed
 
-    def step_buffers(self, B, V=1, want_x0=False, edit=False) -> engine.StepBuffers:
+    def step_buffers(self, B, V=1, want_x0=False, edit=False, plms=False) -> engine.StepBuffers:
         """The device buffers of a loop over B clips x V variants (cached).  (Named so that `nn.Module.buffers()` stays what PyTorch's wrappers -
         nn.DataParallel.forward, the reference's default wrap, train.py:94 - expect it to be.)"""
-        k = (B, V, want_x0, self.m_tile, self.layer_mode, edit)
+        k = (B, V, want_x0, self.m_tile, self.layer_mode, edit, plms)
         bufs = self.__dict__.setdefault("_syn_bufs", {})
         if k not in bufs:
             if len(bufs) > 4:
                 bufs.clear()
             # (`edit` is passed only when set: stand-ins for StepBuffers with the six-argument signature keep working for plain loops)
             bufs[k] = engine.StepBuffers(B, V, next(self.parameters()).device, want_x0, self.m_tile, self.layer_mode,
-                                         **({"edit": True} if edit else {}))
+                                         **({"edit": True} if edit else {}), **({"plms": True} if plms else {}))
         return bufs[k]
 
     def variant_conds(self, y: dict, variants) -> torch.Tensor:

@@ -147,10 +147,14 @@ class PackedModel:
 class StepBuffers:
     """State + workspace for B clips x V conditioning variants; owns the syn_step struct."""
 
-    def __init__(self, B: int, V: int, device, want_x0: bool = False, m_tile: int = 0, layer_mode: int = 0, edit: bool = False):
+    def __init__(self, B: int, V: int, device, want_x0: bool = False, m_tile: int = 0, layer_mode: int = 0, edit: bool = False,
+                 plms: bool = False):
         """``edit``: the buffers carry an in-painting mask and motion (`load_edit`) and every step blends them in
-        (`syn_denoise_step_edit`)."""
+        (`syn_denoise_step_edit`).  ``plms``: they also carry what the multistep sampler keeps between steps (`PlmsLoop`): a second
+        latent the steps ping-pong with, the ring of three earlier noise estimates, and pred_x0; H, the weighted history a step
+        injects, is the `noise` operand."""
         self.B, self.V = B, V
+        want_x0 = want_x0 or plms
         # latent layout: fragment order when the wave-per-sequence kernel runs the steps (the library's choice for large
         # single-variant batches, or pinned with layer_mode 5), token-major otherwise - and always with an edit, which that kernel
         # does not take
@@ -204,6 +208,12 @@ class StepBuffers:
         if edit:
             self.edit = _lib.SynEdit()
             self.edit.keep, self.edit.known = self.keep.data_ptr(), self.known.data_ptr()
+        self.plms = plms
+        if plms:
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
+            self.x2, self.xb2, self.ring = z(Mb, CH), z(Mb, CH, dt=bf), z(3, Mb, CH)
+            for t in (self.x, self.xb, self.noise, self.x0):       # (the capture's warm-up launch runs on them as they stand)
+                t.zero_()
 
     # layout ------------------------------------------------------------------------------------
     def _import(self, src: torch.Tensor, dst_f32, dst_bf16):
@@ -409,3 +419,175 @@ def ddim_coefs(tab: dict, eta: float, device) -> torch.Tensor:
 def identity_coefs(device) -> torch.Tensor:
     """x_next = x0: a bare model evaluation (MDM.forward)."""
     return torch.tensor([[1.0, 0.0, 0.0, 0.0]], dtype=torch.float32, device=device)
+
+
+# ---- pseudo linear multistep (gaussian_diffusion.py:1004-1086) -------------------------------------------------------------------------
+AB_WEIGHTS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}     # Adams-Bashforth
+
+
+def plms_coefs(tab: dict, order: int, n_steps: int) -> dict:
+    """The PLMS loop over timesteps n_steps - 1 .. 0 as n_steps + 1 launches of the step kernel, each followed by `syn_plms_update`, in fp64.
+
+    With r, m = sqrt_recip / sqrt_recipm1_alphas_cumprod[t], p, q = sqrt(ab_prev[t]), sqrt(1 - ab_prev[t]), beta = q - p m and a_0..a_3 the
+    Adams-Bashforth weights of the step's current order, the reference's x_next = p (r x_t - m eps') + q eps', eps' = a_0 eps + sum a_k e_k,
+    eps = (r x_t - x0_hat) / m, is
+        x_next = c_x0 x0_hat + c_xt x_t + beta H,   c_x0 = -beta a_0 / m,   c_xt = r (p + beta a_0 / m),   H = sum_{k >= 1} a_k e_k
+    (a_0 = 1, H = 0: the DDIM eta = 0 row; t == 0: (1, 0, 0), the sample is pred_xstart).  The first step, two model calls (:1054-1061):
+    launch 0 is the DDIM row at t into the other latent, its update keeps e_1 and leaves H = p r x_T + beta e_1 / 2; launch 1 evaluates the
+    model there at t - 1 with the row (-beta / (2 m'), beta r' / (2 m'), 1), i.e. x_next = H + beta e_2 / 2, and e_2 is not kept.
+
+    Rows by launch: "coef" (c_x0, c_xt, sigma, 0); "hist" (r, 1 / m, h_x, w_new, w[0..2]) and "store" as `syn_plms_row`; "t" the timestep of the
+    launch's model call; "order" the current order of its step (1: the Euler start).  Estimate j (0: e_1 of the start, j: step j's) lives in
+    ring slot j % 3."""
+    if order not in (2, 3, 4):
+        raise ValueError("order is 2, 3 or 4")
+    n = int(n_steps)
+    if n < 2 or n > len(tab["betas"]):
+        raise ValueError(f"a PLMS loop takes 2 .. {len(tab['betas'])} steps (its first step calls the model at t and t - 1)")
+    r_, m_ = np.asarray(tab["sqrt_recip_alphas_cumprod"], np.float64), np.asarray(tab["sqrt_recipm1_alphas_cumprod"], np.float64)
+    abp = np.asarray(tab["alphas_cumprod_prev"], np.float64)
+    p_, q_ = np.sqrt(abp), np.sqrt(1.0 - abp)
+    beta_ = q_ - p_ * m_
+    L = n + 1
+    coef, hist, store = np.zeros((L, 4), np.float64), np.zeros((L, 7), np.float64), np.full(L, -1, np.int64)
+    ts, orders = np.zeros(L, np.int64), np.ones(L, np.int64)
+    t0 = n - 1
+    r, m, p, q, beta = r_[t0], m_[t0], p_[t0], q_[t0], beta_[t0]
+    ts[0], ts[1] = t0, t0 - 1
+    coef[0] = (p - q / m, q * r / m, 0.0, 0.0)
+    hist[0, :4], store[0] = (r, 1.0 / m, p * r, beta / 2), 0
+    coef[1] = (-beta / (2 * m_[t0 - 1]), beta * r_[t0 - 1] / (2 * m_[t0 - 1]), 1.0, 0.0)
+    hist[1, :2] = (r_[t0 - 1], 1.0 / m_[t0 - 1])
+
+    def history(row, j_next, newest_in_register):
+        """H of step j_next into `row`: estimate j_next - k has weight a_k; the newest one may still be in the update's registers."""
+        if j_next > n - 1 or n - 1 - j_next == 0:            # nothing follows, or the t == 0 step: sigma = 0
+            return
+        a = AB_WEIGHTS[min(order, j_next + 1)]
+        for k in range(1, len(a)):
+            if k == 1 and newest_in_register:
+                hist[row, 3] = a[k]
+            else:
+                hist[row, 4 + (j_next - k) % 3] = a[k]
+    history(1, 1, False)
+    for j in range(1, n):
+        t, row = n - 1 - j, j + 1
+        ts[row], orders[row] = t, min(order, j + 1)
+        a0 = AB_WEIGHTS[orders[row]][0]
+        coef[row] = (1.0, 0.0, 0.0, 0.0) if t == 0 else (-beta_[t] * a0 / m_[t], r_[t] * (p_[t] + beta_[t] * a0 / m_[t]), beta_[t], 0.0)
+        hist[row, :2] = (r_[t], 1.0 / m_[t])
+        history(row, j + 1, True)
+        if order > 2 and j + 2 <= n - 2:          # read again after the next step (which takes it from this update's registers)
+            store[row] = j % 3
+    return {"coef": coef, "hist": hist, "store": store, "t": ts, "order": orders}
+
+
+class PlmsLoop:
+    """The captured graphs of PLMS loops over one StepBuffers (plms=True): every launch is `syn_step_advance`, the step, `syn_plms_update`.
+    The step must not overwrite the x_t its update reads, so consecutive steps ping-pong between sb.x and sb.x2 (no bytes moved; the other
+    choice, the update moving the result into place, is 10 more bytes per element) - one graph per direction, "start" for the two launches of
+    the first step, and `MULTI` steps in one graph for stretches without hooks (an even count: it ends on the latent it started from).
+    Coefficient and history tables sit in fixed device buffers (`load`), so the graphs outlive a loop and serve any order and step count."""
+
+    MAX_ROWS, MULTI = StepGraph.MAX_STEPS, 10
+
+    def __init__(self, pm: PackedModel, sb: StepBuffers):
+        assert sb.plms
+        dev = pm.device
+        self.pm, self.sb = pm, sb
+        self.sched = torch.zeros(self.MAX_ROWS, 2, dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.coef = torch.zeros(self.MAX_ROWS, 4, dtype=torch.float32, device=dev)
+        self.rows = torch.zeros(self.MAX_ROWS, C.sizeof(_lib.SynPlmsRow), dtype=torch.uint8, device=dev)
+        self.tm_rows = torch.zeros(self.MULTI, sb.t_model.numel(), dtype=torch.int32, device=dev)
+        self.tc_rows = torch.zeros(self.MULTI, sb.t_coef.numel(), dtype=torch.int32, device=dev)
+        self.lat = ((sb.x, sb.xb), (sb.x2, sb.xb2))
+        self.graphs, self.loaded = {}, None
+        # warm-up launches outside capture (module load etc.), on the zeroed tables: row 0 keeps an all-zero estimate in ring slot 0
+        sb.t_model.zero_(); sb.t_coef.zero_()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._issue("start")
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.counter.zero_()
+
+    def _step(self, parity: int, back: int, tm_ptr: int, tc_ptr: int, want_x0: bool = True):
+        """One step from latent `parity` into the other, then the history update on what it read."""
+        sb, c = self.sb, self.sb.c
+        saved = {f: getattr(c, f) for f in ("x_t", "x_t_bf16", "x_next", "x_next_bf16", "t_model", "t_coef", "pred_x0")}
+        (x, xb), (y, yb) = self.lat[parity], self.lat[1 - parity]
+        try:
+            c.x_t, c.x_t_bf16, c.x_next, c.x_next_bf16 = x.data_ptr(), xb.data_ptr(), y.data_ptr(), yb.data_ptr()
+            c.t_model, c.t_coef = tm_ptr, tc_ptr
+            c.pred_x0 = sb.x0.data_ptr() if want_x0 else None
+            run_step(self.pm, sb, self.coef, use_noise=True, fused_rng=False)
+        finally:
+            for f, v in saved.items():
+                setattr(c, f, v)
+        _lib.check(_lib.load().syn_plms_update(self.rows.data_ptr(), self.MAX_ROWS, self.counter.data_ptr(), back, x.data_ptr(),
+                                               sb.x0.data_ptr(), sb.ring.data_ptr(), sb.noise.data_ptr(), x.numel(),
+                                               _lib.current_stream(self.pm.device)), "syn_plms_update")
+
+    def _issue(self, kind):
+        sb, lib, stream = self.sb, _lib.load(), _lib.current_stream(self.pm.device)
+        n_tm, n_tc = sb.t_model.numel(), sb.t_coef.numel()
+        advance = lambda: _lib.check(lib.syn_step_advance(self.sched.data_ptr(), self.counter.data_ptr(), sb.t_model.data_ptr(), n_tm,
+                                                          sb.t_coef.data_ptr(), n_tc, stream), "syn_step_advance")
+        if kind == "start":
+            # the second model call's x0_hat is not the step's pred_xstart (:1086) and its estimate is not kept: pred_x0 = NULL there
+            advance(); self._step(0, 1, sb.t_model.data_ptr(), sb.t_coef.data_ptr())
+            advance(); self._step(1, 1, sb.t_model.data_ptr(), sb.t_coef.data_ptr(), want_x0=False)
+        elif kind == "multi":
+            _lib.check(lib.syn_steps_advance(self.sched.data_ptr(), self.counter.data_ptr(), self.tm_rows.data_ptr(), n_tm,
+                                             self.tc_rows.data_ptr(), n_tc, self.MULTI, stream), "syn_steps_advance")
+            for j in range(self.MULTI):
+                self._step(j % 2, self.MULTI - j, self.tm_rows[j].data_ptr(), self.tc_rows[j].data_ptr())
+        else:
+            advance(); self._step(kind, 1, sb.t_model.data_ptr(), sb.t_coef.data_ptr())
+
+    def issue(self, kind, eager: bool = False):
+        """"start", "multi", or the parity 0 / 1 of a single step: a replay of its graph (captured at first use), or the same launches eagerly."""
+        if eager:
+            return self._issue(kind)
+        g = self.graphs.get(kind)
+        if g is None:
+            g = self.graphs[kind] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._issue(kind)
+        g.replay()
+
+    def load(self, key, make, t_model_of):
+        """Tables of the coming loop (`make()` -> `plms_coefs`), launch schedule from the start; `t_model_of`: timestep -> the model's."""
+        if self.loaded != key:
+            tab = make()
+            L = len(tab["store"])
+            if L > self.MAX_ROWS:
+                raise ValueError(f"a PLMS loop of {L - 1} steps exceeds {self.MAX_ROWS - 1}")
+            rows = np.zeros(L, dtype=[("f", np.float32, 7), ("store", np.int32)])
+            rows["f"], rows["store"] = tab["hist"], tab["store"]
+            self.rows[:L].copy_(torch.from_numpy(rows.view(np.uint8).reshape(L, -1)))
+            self.coef[:L].copy_(torch.from_numpy(tab["coef"].astype(np.float32)))
+            sched = np.stack([np.arange(L), [t_model_of(int(t)) for t in tab["t"]]], 1).astype(np.int32)
+            self.sched[:L].copy_(torch.from_numpy(sched))
+            self.loaded, self.n_launches = key, L
+        self.counter.zero_()
+        self.sb.noise.zero_()                 # launch 0 has sigma = 0, but 0 * H must be 0
+
+    def run(self, each=None, eager: bool = False) -> torch.Tensor:
+        """The loaded loop on the latent in sb.x; returns the fp32 latent that holds the result (sb.x or sb.x2).  `each(k, x)` after step k."""
+        n = self.n_launches - 1
+        self.issue("start", eager)
+        if each is not None:
+            each(0, self.sb.x)
+        j = 1
+        while each is None and n - j >= self.MULTI:
+            self.issue("multi", eager)
+            j += self.MULTI
+        while j < n:
+            parity = (j - 1) % 2
+            self.issue(parity, eager)
+            if each is not None:
+                each(j, self.lat[1 - parity][0])
+            j += 1
+        return self.lat[(n - 1) % 2][0]

@@ -82,7 +82,7 @@ def window_edit(i: int, known_latent, keep, round_l: int, window: int = 32, sque
 def sample_long(diffusion, model, audio, word, seed_latent, n_pose: int | None = None, *, pose_length: int = 128,
                 pre_frames: int = 4, squeeze: int = 4, use_ddim: bool = False, style_dim: int = 512, noise_fn=None,
                 step_noise_fn=None, seed: int | None = None, skip_timesteps: int = 0, progress: bool = False, y_extra: dict | None = None,
-                edit=None):
+                edit=None, sampler: str | None = None, plms_order: int = 2):
     """Returns latents (B, rounds*round_l/squeeze + pre_frames, 1536): window 0 whole, later windows without their
     first pre_frames rows (trainer lines 468-476).
     noise_fn(i) -> x_T of window i or None (library draws it); step_noise_fn(i) -> injected per-step noise or None;
@@ -93,7 +93,12 @@ def sample_long(diffusion, model, audio, word, seed_latent, n_pose: int | None =
     n_pose = word.shape[1] if n_pose is None else n_pose
     round_l, rounds, _ = window_plan(n_pose, pose_length, pre_frames, squeeze)
     bs = word.shape[0]
-    loop = diffusion.ddim_sample_loop if use_ddim else diffusion.p_sample_loop
+    sampler = sampler or ("ddim" if use_ddim else "ddpm")
+    if sampler not in ("ddpm", "ddim", "plms"):
+        raise ValueError(f"unknown sampler {sampler!r}: ddpm, ddim or plms")
+    loop = getattr(diffusion, {"ddpm": "p_sample_loop", "ddim": "ddim_sample_loop", "plms": "plms_sample_loop"}[sampler])
+    if sampler == "plms" and step_noise_fn is not None:
+        raise ValueError("the PLMS sampler draws no per-step noise: step_noise_fn does not apply")
     if edit is not None:
         known_latent, keep = edit
         if keep.dtype is not torch.bool:
@@ -104,7 +109,7 @@ def sample_long(diffusion, model, audio, word, seed_latent, n_pose: int | None =
         y = window_inputs(i, audio, word, seed_latent, last, round_l, pre_frames, squeeze, style_dim, y_extra)
         if edit is not None:
             y["inpainted_motion"], y["inpainting_mask"] = window_edit(i, known_latent, keep, round_l, pose_length // squeeze, squeeze)
-        kw = {}
+        kw = {"order": plms_order} if sampler == "plms" else {}
         if step_noise_fn is not None:
             kw["step_noise"] = step_noise_fn(i)
         if seed is not None:

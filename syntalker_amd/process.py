@@ -3,14 +3,14 @@
 API surface kept (seam 2): ``create_gaussian_diffusion(DiffusionClass=SpacedDiffusion,
 use_ddim=False)`` returning an object with ``num_timesteps``, ``timestep_map``, the fp64 numpy tables
 under their reference names, ``q_sample``, ``p_mean_variance``, ``p_sample``, ``p_sample_loop``
-(+ ``_progressive``), ``ddim_sample``, ``ddim_sample_loop`` (+ ``_progressive``) and
-``training_losses`` with the reference's keyword arguments.
+(+ ``_progressive``), ``ddim_sample``, ``ddim_sample_loop`` (+ ``_progressive``), ``plms_sample``,
+``plms_sample_loop`` (+ ``_progressive``) and ``training_losses`` with the reference's keyword arguments.
 
 What is different underneath:
   * the schedule tables live on the device once (the reference re-uploads a 1000-entry fp64 table on
     every ``_extract_into_tensor`` call, gaussian_diffusion.py:1606-1619, ~8 H2D copies per step);
   * when the model resolves to a HIP ``MDM`` (optionally under the guidance wrappers / DataParallel),
-    ``p_sample_loop`` / ``ddim_sample_loop`` run the FUSED loop: conditioning hoisted out of the loop,
+    ``p_sample_loop`` / ``ddim_sample_loop`` / ``plms_sample_loop`` run the FUSED loop: conditioning hoisted out of the loop,
     x kept token-major on the device, one hipGraph replay per step with the posterior / DDIM update
     fused into the output GEMM's epilogue (engine.py, csrc/syn_kernels.hip);
   * any other model goes through the generic per-step path (same arithmetic in torch ops).
@@ -24,6 +24,8 @@ differ; ``seed`` — key of the counter-based in-library generator used when no 
 from __future__ import annotations
 
 import enum
+import functools
+import inspect
 import math
 
 import numpy as np
@@ -97,6 +99,28 @@ _TABLES = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_nex
            "sqrt_one_minus_alphas_cumprod", "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
            "posterior_mean_coef1", "posterior_mean_coef2")
+
+
+class UnboundCall(TypeError, NotImplementedError):
+    """A call that does not bind to the parameters of one of the `plms_*` methods.  Until they were built every call of them raised
+    NotImplementedError naming the reference line; a call that cannot be a sampler call at all (a probe, `plms_sample_loop(None)`) still
+    does, and is the TypeError Python makes of it as well."""
+
+
+def _names_reference_line(where):
+    """Decorator of a method built after callers met it as `_unsupported`: see `UnboundCall`.  Calls that bind go straight through."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def method(self, *a, **k):
+            try:
+                sig.bind(self, *a, **k)
+            except TypeError as e:
+                raise UnboundCall(f"GaussianDiffusion.{fn.__name__} (reference diffusion/gaussian_diffusion.py:{where}): {e}") from None
+            return fn(self, *a, **k)
+        return method
+    return deco
 
 
 class GaussianDiffusion:
@@ -269,6 +293,49 @@ class GaussianDiffusion:
         abn = self._tab("alphas_cumprod_next", t, x)
         return {"sample": out["pred_xstart"] * torch.sqrt(abn) + torch.sqrt(1 - abn) * eps, "pred_xstart": out["pred_xstart"]}
 
+    @staticmethod
+    def _plms_order(order):
+        """gaussian_diffusion.py:1022-1023, and order 1, which the reference accepts there and then fails on (:1064)."""
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= order <= 4:
+            raise ValueError("order is invalid (should be int from 1-4).")
+        if order == 1:
+            raise ValueError("order=1 has no reference behaviour: gaussian_diffusion.py:1064 reads old_out['old_eps'] with old_out = None on the "
+                             "first step (TypeError); use order 2, 3 or 4")
+        return int(order)
+
+    @_names_reference_line("1004")
+    def plms_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, cond_fn_with_grad=False,
+                    order=2, old_out=None):
+        """gaussian_diffusion.py:1004-1086: one pseudo linear multistep step (generic path).  Without `old_out` the two-call "pseudo improved
+        Euler" start; then Adams-Bashforth over `old_out["old_eps"]`, which this call extends (and returns) like the reference."""
+        order = self._plms_order(order)
+        if cond_fn is not None or cond_fn_with_grad:
+            raise NotImplementedError("cond_fn (classifier guidance) is never used by the reference's callers")
+
+        def estimate(x, t):
+            out = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+            return self._predict_eps_from_xstart(x, t, out["pred_xstart"]), out
+        abp = self._tab("alphas_cumprod_prev", t, x)
+        eps, out = estimate(x, t)
+        if old_out is None:
+            if bool((t < 1).any()):
+                raise ValueError("the first PLMS step calls the model at t - 1: it cannot start at t = 0 (a loop of fewer than 2 steps)")
+            old_eps = [eps]
+            eps_2, _ = estimate(out["pred_xstart"] * torch.sqrt(abp) + torch.sqrt(1 - abp) * eps, t - 1)
+            eps_prime = (eps + eps_2) / 2
+        else:
+            old_eps = old_out["old_eps"]
+            old_eps.append(eps)
+            a = engine.AB_WEIGHTS[min(order, len(old_eps))]
+            eps_prime = a[0] * old_eps[-1]
+            for k in range(1, len(a)):
+                eps_prime = eps_prime + a[k] * old_eps[-1 - k]
+        mean = self._predict_xstart_from_eps(x, t, eps_prime) * torch.sqrt(abp) + torch.sqrt(1 - abp) * eps_prime
+        if len(old_eps) >= order:
+            old_eps.pop(0)
+        nz = self._nonzero(t, x)
+        return {"sample": mean * nz + out["pred_xstart"] * (1 - nz), "pred_xstart": out["pred_xstart"], "old_eps": old_eps}
+
     # What the reference's GaussianDiffusion also defines and none of its trainers, tests or demos reaches: explicit errors
     # naming the reference lines instead of AttributeError.
     def _unsupported(name, where):
@@ -278,7 +345,7 @@ class GaussianDiffusion:
                                       "not built")
         method.__name__ = name
         return method
-    for _n, _w in (("plms_sample", "1004"), ("plms_sample_loop", "1088"), ("plms_sample_loop_progressive", "1130"), ("_vb_terms_bpd", "1201"),
+    for _n, _w in (("_vb_terms_bpd", "1201"),
                    ("_prior_bpd", "1530"), ("calc_bpd_loop", "1548"), ("p_sample_with_grad", "559"), ("ddim_sample_with_grad", "793"),
                    ("condition_mean", "427"), ("condition_mean_with_grad", "442"), ("condition_score", "457"), ("condition_score_with_grad", "481")):
         locals()[_n] = _unsupported(_n, _w)
@@ -318,11 +385,11 @@ class GaussianDiffusion:
 
     @property
     def last_path(self):
-        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` call took (None before the first)."""
+        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` / `plms_sample_loop` call took (None before the first)."""
         return getattr(self, "_last_path", None)
 
     def _fused(self, kind, mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image, step_noise,
-               seed, progress, each=None, first_clip=0):
+               seed, progress, each=None, first_clip=0, order=None):
         """The whole loop on the device.  A batch between two pass sizes of the wave-per-sequence kernel runs as two
         slices, one after the other (`engine.plan_slices`): clips are independent and every random draw is keyed by the
         global clip index, so the slices' results are the batch's."""
@@ -335,7 +402,7 @@ class GaussianDiffusion:
                 slices = engine.plan_slices(B, len(plan_fn(model_kwargs["y"]).variants), dev)
         if len(slices) == 1:
             return self._fused_slice(kind, mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image,
-                                     step_noise, seed, progress, each, first_clip)
+                                     step_noise, seed, progress, each, first_clip, order=order)
         if seed is None and step_noise is None and (kind == "ddpm" or eta != 0.0):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # one seed for all slices
         if noise is None:
@@ -351,13 +418,14 @@ class GaussianDiffusion:
             outs.append(self._fused_slice(kind, mdm, plan_fn, (hi - lo,) + tuple(shape[1:]), cut(noise, lo, hi), kw, eta,
                                           skip_timesteps, cut(init_image, lo, hi),
                                           None if step_noise is None else step_noise[:, lo:hi], seed, False, None,
-                                          first_clip + lo, conds=conds[:, lo:hi]))
+                                          first_clip + lo, conds=conds[:, lo:hi], order=order))
         return torch.cat(outs, 0)
 
     def _fused_slice(self, kind, mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image, step_noise,
-                     seed, progress, each=None, first_clip=0, conds=None):
+                     seed, progress, each=None, first_clip=0, conds=None, order=None):
         """x stays on the device in the step kernel's layout for the whole loop; one graph replay per step (ten steps per
-        replay where nothing happens in between)."""
+        replay where nothing happens in between).  kind "plms": `engine.PlmsLoop`'s graphs - every replay is the step and the update
+        of the history of noise estimates; `each(k, sb, x)` gets the latent that holds step k's sample."""
         dev = next(mdm.parameters()).device
         y = model_kwargs["y"]
         B = shape[0]
@@ -365,7 +433,17 @@ class GaussianDiffusion:
             plan = plan_fn(y)
             V = len(plan.variants)
             edit = "inpainting_mask" in y                                   # (`_fusable` has checked the pair)
-            pm, sb = mdm.packed(), mdm.step_buffers(B, V, want_x0=each is not None, edit=edit)
+            plms = kind == "plms"
+            pm, sb = mdm.packed(), mdm.step_buffers(B, V, want_x0=plms or each is not None, edit=edit, **({"plms": True} if plms else {}))
+            if plms:
+                # (the graphs' warm-up launch runs on the latent: before it is loaded)
+                loops = mdm.__dict__.setdefault("_syn_graphs", {})
+                lkey = ("plms", id(pm), id(sb))
+                if lkey not in loops:
+                    if len(loops) > 8:
+                        loops.clear()
+                    loops[lkey] = engine.PlmsLoop(pm, sb)
+                loop = loops[lkey]
             if edit:
                 sb.load_edit(y["inpainting_mask"], y["inpainted_motion"])
             sb.cond.copy_((mdm.variant_conds(y, plan.variants) if conds is None else conds).reshape(-1, engine.D))
@@ -373,6 +451,19 @@ class GaussianDiffusion:
                 sb.cfg_w.copy_(plan.tensor(dev))
             img, indices = self._start(shape, None if noise is None else noise.to(dev), dev, skip_timesteps, init_image)
             sb.load_x(img)
+            if plms:
+                _, tmap = self._model_timesteps(dev)
+                n = len(indices)
+                loop.load((hash(self.betas.tobytes()), order, n), lambda: engine.plms_coefs(self.tables(), order, n), lambda t: int(tmap[t]))
+                hook = None if each is None else (lambda k, x: each(k, sb, x))
+                if progress:
+                    try:
+                        from tqdm.auto import tqdm
+                        bar, inner = tqdm(total=n), hook
+                        hook = lambda k, x: (bar.update(1), inner(k, x) if inner is not None else None)
+                    except ImportError:
+                        pass
+                return sb.read(loop.run(hook))
             if kind == "ddpm":
                 coef = self._cached(("coef", "ddpm", dev), lambda: engine.posterior_coefs(self.tables(), dev))
                 noisy = True
@@ -500,6 +591,59 @@ class GaussianDiffusion:
         for out in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                                                      model_kwargs, device, progress, eta, skip_timesteps, init_image,
                                                      randomize_class, cond_fn_with_grad, step_noise=step_noise):
+            final = out
+        return final["sample"]
+
+    @_names_reference_line("1130")
+    def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                     device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
+                                     cond_fn_with_grad=False, order=2):
+        """gaussian_diffusion.py:1130-1199 (generic path): yields every step's {"sample", "pred_xstart", "old_eps"}."""
+        order = self._plms_order(order)
+        if randomize_class or cond_fn_with_grad:
+            raise NotImplementedError("randomize_class / cond_fn_with_grad are never used by the reference's callers")
+        if self.num_timesteps - skip_timesteps < 2:
+            raise ValueError("a PLMS loop takes at least 2 steps: its first step calls the model at t and t - 1 "
+                             "(the reference would index timestep -1, gaussian_diffusion.py:1058)")
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        img, indices = self._start(shape, noise, device, skip_timesteps, init_image)
+        if progress:
+            try:
+                from tqdm.auto import tqdm
+                indices = tqdm(indices)
+            except ImportError:
+                pass
+        old_out = None
+        for i in indices:
+            t = torch.full((shape[0],), i, device=img.device, dtype=torch.long)
+            with torch.no_grad():
+                out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                       model_kwargs=model_kwargs, cond_fn_with_grad=cond_fn_with_grad, order=order, old_out=old_out)
+            yield out
+            old_out, img = out, out["sample"]
+
+    @_names_reference_line("1088")
+    def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
+                         cond_fn_with_grad=False, order=2, *, seed=None, first_clip=0):
+        """gaussian_diffusion.py:1088-1128.  On the fused path under `p_sample_loop`'s conditions (in-painting operands included: the
+        noise estimates derive from the blended pred_xstart, as in the reference).  The sampler draws nothing after x_T: ``seed`` and
+        ``first_clip`` are accepted for symmetry with the other loops and change no result."""
+        order = self._plms_order(order)
+        if self.num_timesteps - skip_timesteps < 2:
+            raise ValueError("a PLMS loop takes at least 2 steps: its first step calls the model at t and t - 1 "
+                             "(the reference would index timestep -1, gaussian_diffusion.py:1058)")
+        mdm, plan_fn = self._fusable(model, model_kwargs, denoised_fn, cond_fn, clip_denoised, False, randomize_class,
+                                     cond_fn_with_grad, shape)
+        self._last_path = "generic" if mdm is None else "fused"
+        if mdm is not None:
+            return self._fused("plms", mdm, plan_fn, shape, noise, model_kwargs, 0.0, skip_timesteps, init_image, None, seed,
+                               progress, None, first_clip, order=order)
+        final = None
+        for out in self.plms_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                                                     progress, skip_timesteps, init_image, randomize_class, cond_fn_with_grad, order):
             final = out
         return final["sample"]
 
