@@ -191,6 +191,26 @@ typedef struct syn_plms_row {
 int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
                     float* ring, float* h, int64_t n, void* stream);
 
+/* The variational bound per timestep (diffusion/gaussian_diffusion.py:1201-1234, 1548-1603: calc_bpd_loop / _vb_terms_bpd).  No timestep of
+ * that loop depends on another, so clips x timesteps are one batch of independent sequences: syn_denoise_step evaluates the model on all of
+ * them (t_model / t_coef hold one timestep per sequence) and syn_bpd_terms reduces each to the loop's three scalars.  One row per timestep: */
+typedef struct syn_bpd_row {
+    float   c1, c2;     /* posterior_mean_coef1 / 2[t]: mean = c1 * pred_x0 + c2 * x_t                                                    */
+    float   log_var;    /* posterior_log_variance_clipped[t] (FIXED_SMALL: the log-variance of q's posterior and of p)                     */
+    float   r, inv_m;   /* eps = (r * x_t - pred_x0) * inv_m, as syn_plms_row                                                              */
+    int32_t first;      /* nonzero at t == 0: vb is the decoder NLL (diffusion/losses.py discretized_gaussian_log_likelihood), else the KL */
+} syn_bpd_row;
+
+/* Sequence i of n_seq: row t_row[i] of table [n_rows], x_start of clip clip[i] (clip = NULL: clip i, n_seq <= n_clips), its own 49 152
+ * floats of x_t, noise and pred_x0 -> out [3][n_seq]: vb in bits per dimension, xstart_mse = mean((pred_x0 - x_start)^2), mse =
+ * mean((eps - noise)^2).  An index outside its table gives NaN in the three outputs of that sequence and reads nothing.  One workgroup per
+ * sequence, no atomics; the sum over a sequence's 16-byte groups is exact (csrc/syn_bpd.inc), so a sequence's outputs are bitwise the same
+ * on every run, whatever n_seq is and whichever sequences share the launch, and for every order of the groups: a sequence's floats are
+ * contiguous in both latent layouts and the kernel does not care which it is given, provided the four tensors share it.  x_start, x_t,
+ * noise and pred_x0 16-byte aligned.  Enqueues on `stream`, allocates nothing, graph-capturable. */
+int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
+                  const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

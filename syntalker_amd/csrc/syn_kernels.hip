@@ -1752,6 +1752,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_skel.inc"
 #include "syn_t2m.inc"
 #include "syn_plms.inc"
+#include "syn_bpd.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2250,6 +2251,11 @@ int syn_step_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, i
 int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
                     float* ring, float* h, int64_t n, void* stream) {
     return plms::update(table, n_rows, counter, back, x_t, pred_x0, ring, h, n, stream);
+}
+
+int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
+                  const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream) {
+    return bpd::terms(table, n_rows, t_row, clip, x_start, n_clips, x_t, noise, pred_x0, n_seq, out, stream);
 }
 
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {

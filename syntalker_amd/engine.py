@@ -591,3 +591,126 @@ class PlmsLoop:
                 each(j, self.lat[1 - parity][0])
             j += 1
         return self.lat[(n - 1) % 2][0]
+
+
+# ---- the variational bound per timestep (gaussian_diffusion.py:1201-1234, 1548-1603) ---------------------------------------------------
+BPD_ROW = np.dtype([("c1", np.float32), ("c2", np.float32), ("log_var", np.float32), ("r", np.float32), ("inv_m", np.float32),
+                    ("first", np.int32)])                                           # include/syn_hip.h syn_bpd_row
+
+
+def bpd_rows(tab: dict) -> np.ndarray:
+    """One `syn_bpd_row` per timestep of the process, from the fp64 tables: the posterior mean's coefficients and log-variance
+    (FIXED_SMALL: q's posterior and p share it, so the KL is 0.5 exp(-log_var) (c1 (x0 - x0_hat))^2), r and 1 / m of
+    eps = (r x_t - x0_hat) / m, and `first` at t == 0, where the term is the decoder's discretised log-likelihood."""
+    rows = np.zeros(len(tab["betas"]), BPD_ROW)
+    rows["c1"], rows["c2"] = tab["posterior_mean_coef1"], tab["posterior_mean_coef2"]
+    rows["log_var"] = tab["posterior_log_variance_clipped"]
+    rows["r"] = tab["sqrt_recip_alphas_cumprod"]
+    rows["inv_m"] = 1.0 / np.asarray(tab["sqrt_recipm1_alphas_cumprod"], np.float64)
+    rows["first"][0] = 1
+    return rows
+
+
+def bpd_chunks(n_pairs: int, n_variants: int, device, chunk=None) -> list[tuple[int, int]]:
+    """Ranges of the (clip, timestep) pairs a call runs as, one after the other.  ``chunk`` pairs each when given; else full passes of the
+    wave-per-sequence kernel (`seq_pass_clips`), the last of them together with the remainder as `plan_slices` runs that many clips."""
+    if chunk is not None:
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+            raise ValueError("chunk is a positive number of (clip, timestep) pairs")
+        return [(lo, min(lo + int(chunk), n_pairs)) for lo in range(0, n_pairs, int(chunk))]
+    P = seq_pass_clips(n_variants, device)
+    if P == 0 or n_pairs <= P:
+        return [(0, n_pairs)]
+    q, r = divmod(n_pairs, P)
+    lo = (q - 1) * P
+    return [(i * P, (i + 1) * P) for i in range(q - 1)] + [(lo + a, lo + b) for a, b in plan_slices(P + r, n_variants, device)]
+
+
+def seeded_noise(seed: int, first_clip: int, clips, steps, device) -> torch.Tensor:
+    """(n, 1536, 1, 32) N(0,1) for the pairs (clips[k], steps[k]) (host sequences): pair (b, t) is `syn_randn(seed, stream_id = t,
+    first_index = (first_clip + b) * 32 * 1536)` over the clip's latent in token-major order, like the loops' per-step draws - so a
+    draw depends on neither the chunking of a call nor on how clips are sharded over ranks.  Runs of consecutive clips at one timestep
+    are one launch."""
+    lib, n = _lib.load(), len(clips)
+    tm = torch.empty(n, T, CH, dtype=torch.float32, device=device)
+    stream, k = _lib.current_stream(device), 0
+    while k < n:
+        j = k + 1
+        while j < n and steps[j] == steps[k] and clips[j] == clips[j - 1] + 1:
+            j += 1
+        _lib.check(lib.syn_randn(tm[k].data_ptr(), (j - k) * T * CH, int(seed), int(steps[k]), (int(first_clip) + int(clips[k])) * T * CH,
+                                 stream), "syn_randn")
+        k = j
+    out = torch.empty(n, CH, 1, T, dtype=torch.float32, device=device)
+    _lib.check(lib.syn_from_token_major(tm.data_ptr(), n, out.data_ptr(), stream), "syn_from_token_major")
+    return out
+
+
+class BpdBatch:
+    """calc_bpd_loop's (clip, timestep) pairs as batches of independent sequences: per chunk x_t = q_sample(x_start[clip], t, noise), one
+    bare model evaluation of all its sequences (`run_step` with `identity_coefs`, one timestep per sequence), and `syn_bpd_terms` on
+    (x_start, x_t, noise, x0_hat) in the step kernel's layout.  Nothing here waits for the device; `finish` checks the small-batch
+    kernel's flag once.  StepBuffers are the model's cached ones, so chunks of one size share theirs."""
+
+    def __init__(self, mdm, q_sample, rows: np.ndarray, t_model_of, x_start: torch.Tensor, conds: torch.Tensor, cfg_w):
+        dev = x_start.device
+        _require_cuda(x_start, "x_start")
+        self.mdm, self.pm, self.q_sample = mdm, mdm.packed(), q_sample
+        self.n_rows = len(rows)
+        self.rows = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(self.n_rows, -1).copy()).to(dev)
+        self.tmap = torch.tensor([int(t_model_of(t)) for t in range(self.n_rows)], dtype=torch.int32, device=dev)
+        self.x_start = x_start.detach().float().contiguous()
+        self.B, self.V = x_start.shape[0], conds.shape[0]
+        self.conds, self.cfg_w = conds, cfg_w                  # (V, B, 32, 512); None, (3, V) or per clip (B, 3, V)
+        self.ident = identity_coefs(dev)
+        self._x0 = {}                                           # layout -> x_start in it
+        self._used = []
+
+    def _x_start_as(self, sb: StepBuffers) -> torch.Tensor:
+        if sb.fragment not in self._x0:
+            lib = _lib.load()
+            dst = torch.empty(self.B * T, CH, dtype=torch.float32, device=self.x_start.device)
+            fn, name = (lib.syn_x_to_fragment, "syn_x_to_fragment") if sb.fragment else (lib.syn_to_token_major, "syn_to_token_major")
+            _lib.check(fn(self.x_start.data_ptr(), self.B, dst.data_ptr(), None, _lib.current_stream(dst.device)), name)
+            self._x0[sb.fragment] = dst
+        return self._x0[sb.fragment]
+
+    def run(self, clips: torch.Tensor, steps: torch.Tensor, noise: torch.Tensor, out: torch.Tensor, want_pred: bool = False):
+        """clips, steps: int64 [n] on the device (steps: rows of the table, i.e. the spaced timesteps); noise (n, 1536, 1, 32); out [3][n]
+        (vb, xstart_mse, mse).  Returns x0_hat (n, 1536, 1, 32) when asked."""
+        n, V, dev = clips.numel(), self.V, self.x_start.device
+        lib, stream = _lib.load(), _lib.current_stream(dev)
+        sb = self.mdm.step_buffers(n, V, want_x0=True)
+        if not any(sb is s for s in self._used):
+            self._used.append(sb)
+        sb.load_x(self.q_sample(self.x_start[clips], steps, noise))
+        sb.load_noise(noise)
+        sb.cond.copy_(self.conds[:, clips].reshape(-1, D))
+        if V > 1:
+            sb.cfg_w.copy_(self.cfg_w if self.cfg_w.dim() == 2 else self.cfg_w[clips])
+        t32, c32 = steps.to(torch.int32), clips.to(torch.int32)
+        sb.t_model.copy_(self.tmap[steps].repeat(V))
+        sb.t_coef.zero_()
+        # the evaluation must leave x_t alone: x0_hat goes to sb.x0 as the step's x_next (identity row), its bf16 copy over the operand copy
+        c = sb.c
+        saved = (c.x_next, c.pred_x0)
+        try:
+            c.x_next, c.pred_x0 = sb.x0.data_ptr(), None
+            run_step(self.pm, sb, self.ident, use_noise=False)
+        finally:
+            c.x_next, c.pred_x0 = saved
+        assert out.shape == (3, n) and out.is_contiguous()
+        _lib.check(lib.syn_bpd_terms(self.rows.data_ptr(), self.n_rows, t32.data_ptr(), c32.data_ptr(), self._x_start_as(sb).data_ptr(),
+                                     self.B, sb.x.data_ptr(), sb.noise.data_ptr(), sb.x0.data_ptr(), n, out.data_ptr(), stream),
+                   "syn_bpd_terms")
+        del t32, c32                                           # (held until the launch is enqueued)
+        if not want_pred:
+            return None
+        pred = torch.empty(n, CH, 1, T, dtype=torch.float32, device=dev)
+        fn, name = (lib.syn_x_from_fragment, "syn_x_from_fragment") if sb.fragment else (lib.syn_from_token_major, "syn_from_token_major")
+        _lib.check(fn(sb.x0.data_ptr(), n, pred.data_ptr(), stream), name)
+        return pred
+
+    def finish(self):
+        for sb in self._used:
+            sb.check_sync()

@@ -4,7 +4,8 @@ API surface kept (seam 2): ``create_gaussian_diffusion(Diffusion
 use_ddim=False)`` returning an object with ``num_timesteps``, ``timestep_map``, the fp64 numpy tables
 under their reference names, ``q_sample``, ``p_mean_variance``, ``p_sample``, ``p_sample_loop``
 (+ ``_progressive``), ``ddim_sample``, ``ddim_sample_loop`` (+ ``_progressive``), ``plms_sample``,
-``plms_sample_loop`` (+ ``_progressive``) and ``training_losses`` with the reference's keyword arguments.
+``plms_sample_loop`` (+ ``_progressive``), ``calc_bpd_loop`` (+ ``_vb_terms_bpd``, ``_prior_bpd``) and ``training_losses`` with the
+reference's keyword arguments.
 
 What is different underneath:
   * the schedule tables live on the device once (the reference re-uploads a 1000-entry fp64 table on
@@ -101,8 +102,39 @@ _TABLES = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_nex
            "posterior_mean_coef1", "posterior_mean_coef2")
 
 
+def mean_flat(t):
+    """diffusion/nn.py: the mean over everything but the batch dimension."""
+    return t.mean(dim=list(range(1, t.dim())))
+
+
+def normal_kl(mean1, logvar1, mean2, logvar2):
+    """diffusion/losses.py:12-39: KL(N(mean1, exp(logvar1)) || N(mean2, exp(logvar2))) per element; scalars broadcast."""
+    like = next(v for v in (mean1, logvar1, mean2, logvar2) if torch.is_tensor(v))
+    logvar1, logvar2 = (v if torch.is_tensor(v) else torch.tensor(v).to(like) for v in (logvar1, logvar2))
+    return 0.5 * (-1.0 + logvar2 - logvar1 + torch.exp(logvar1 - logvar2) + ((mean1 - mean2) ** 2) * torch.exp(-logvar2))
+
+
+def approx_standard_normal_cdf(x):
+    """diffusion/losses.py:42-47: the tanh form."""
+    return 0.5 * (1.0 + torch.tanh(np.sqrt(2.0 / np.pi) * (x + 0.044715 * torch.pow(x, 3))))
+
+
+def discretized_gaussian_log_likelihood(x, *, means, log_scales):
+    """diffusion/losses.py:50-77: log-probability of the bin of half-width 1/255 around x under N(means, exp(log_scales)^2); the outermost
+    bins (|x| > 0.999) take the whole tail; every log is of a value clamped at 1e-12."""
+    assert x.shape == means.shape == log_scales.shape
+    centered = x - means
+    inv_stdv = torch.exp(-log_scales)
+    cdf_plus = approx_standard_normal_cdf(inv_stdv * (centered + 1.0 / 255.0))
+    cdf_min = approx_standard_normal_cdf(inv_stdv * (centered - 1.0 / 255.0))
+    log_cdf_plus = torch.log(cdf_plus.clamp(min=1e-12))
+    log_one_minus_cdf_min = torch.log((1.0 - cdf_min).clamp(min=1e-12))
+    cdf_delta = cdf_plus - cdf_min
+    return torch.where(x < -0.999, log_cdf_plus, torch.where(x > 0.999, log_one_minus_cdf_min, torch.log(cdf_delta.clamp(min=1e-12))))
+
+
 class UnboundCall(TypeError, NotImplementedError):
-    """A call that does not bind to the parameters of one of the `plms_*` methods.  Until they were built every call of them raised
+    """A call that does not bind to the parameters of one of the `plms_*` / `*bpd*` methods.  Until they were built every call of them raised
     NotImplementedError naming the reference line; a call that cannot be a sampler call at all (a probe, `plms_sample_loop(None)`) still
     does, and is the TypeError Python makes of it as well."""
 
@@ -336,6 +368,133 @@ class GaussianDiffusion:
         nz = self._nonzero(t, x)
         return {"sample": mean * nz + out["pred_xstart"] * (1 - nz), "pred_xstart": out["pred_xstart"], "old_eps": old_eps}
 
+    # ---- the variational bound (gaussian_diffusion.py:1201-1234, 1530-1603) ---------------------------------------------------------
+    @_names_reference_line("1201")
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """gaussian_diffusion.py:1201-1234 (generic path): {"output": per clip the KL between q's posterior and p at t, the decoder's
+        negative log-likelihood where t == 0, in bits per dimension; "pred_xstart"}."""
+        true_mean, _, true_log_variance = self.q_posterior_mean_variance(x_start=x_start, x_t=x_t, t=t)
+        out = self.p_mean_variance(model, x_t, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+        kl = normal_kl(true_mean, true_log_variance, out["mean"], out["log_variance"])
+        kl = mean_flat(kl) / np.log(2.0)
+        decoder_nll = -discretized_gaussian_log_likelihood(x_start, means=out["mean"], log_scales=0.5 * out["log_variance"])
+        assert decoder_nll.shape == x_start.shape
+        decoder_nll = mean_flat(decoder_nll) / np.log(2.0)
+        return {"output": torch.where((t == 0), decoder_nll, kl), "pred_xstart": out["pred_xstart"]}
+
+    @_names_reference_line("1530")
+    def _prior_bpd(self, x_start):
+        """gaussian_diffusion.py:1530-1546: KL(q(x_T | x_0) || N(0, 1)) per clip in bits per dimension (a few torch ops on x_start's device)."""
+        if not torch.is_tensor(x_start):
+            raise UnboundCall(f"GaussianDiffusion._prior_bpd (reference diffusion/gaussian_diffusion.py:1530): x_start is a "
+                              f"{type(x_start).__name__}, not a tensor")
+        t = torch.tensor([self.num_timesteps - 1] * x_start.shape[0], device=x_start.device)
+        qt_mean, _, qt_log_variance = self.q_mean_variance(x_start, t)
+        return mean_flat(normal_kl(mean1=qt_mean, logvar1=qt_log_variance, mean2=0.0, logvar2=0.0)) / np.log(2.0)
+
+    def _bpd_fusable(self, model, x_start, clip_denoised, model_kwargs):
+        if not torch.is_tensor(x_start) or not x_start.is_cuda or x_start.dim() != 4:
+            return None, None
+        y = (model_kwargs or {}).get("y")
+        if isinstance(y, dict) and ("inpainting_mask" in y or "inpainted_motion" in y):       # (in-painting inside the likelihood: generic)
+            return None, None
+        return self._fusable(model, model_kwargs, None, None, clip_denoised, False, False, False, tuple(x_start.shape))
+
+    @_names_reference_line("1548")
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, noise=None, seed=None, first_clip=0, chunk=None,
+                      return_pred_xstart=False):
+        """gaussian_diffusion.py:1548-1603: {"total_bpd", "prior_bpd" (N,), "vb", "xstart_mse", "mse" (N, T)}; column j belongs to
+        t = T - 1 - j, the reference's loop order.
+
+        Fused path (`last_path`), under the loops' conditions - a HIP `MDM` in eval mode, possibly under guidance wrappers,
+        clip_denoised=False, x_start (N, 1536, 1, 32) on the device, no in-painting keys: no timestep depends on another, so the N T
+        (clip, timestep) pairs run as batches of independent sequences (`engine.BpdBatch`, `syn_bpd_terms`), ``chunk`` pairs at a time
+        (default: `engine.bpd_chunks`), with one wait for the device at the end.  Anything else: the reference's loop in torch ops.
+
+        ``noise``: (T, N, 1536, 1, 32), row i is iteration i's draw (t = T - 1 - i).  Without it the draws come from the counter-based
+        generator keyed by ``seed`` (default: drawn from torch's generator), the timestep and the global clip index ``first_clip`` + b
+        (`engine.seeded_noise`; on the generic path off the device: from a torch.Generator seeded with ``seed``, or torch's own).
+        ``return_pred_xstart``: also "pred_xstart" (T, N, 1536, 1, 32), in loop order."""
+        if not torch.is_tensor(x_start):
+            raise UnboundCall("GaussianDiffusion.calc_bpd_loop (reference diffusion/gaussian_diffusion.py:1548): x_start is a "
+                              f"{type(x_start).__name__}, not a tensor")
+        T, B = self.num_timesteps, x_start.shape[0]
+        if noise is not None and (not torch.is_tensor(noise) or tuple(noise.shape) != (T, B) + tuple(x_start.shape[1:])):
+            raise ValueError(f"noise must have shape {(T, B) + tuple(x_start.shape[1:])}: one draw per timestep and clip, in loop order")
+        mdm, plan_fn = self._bpd_fusable(model, x_start, clip_denoised, model_kwargs)
+        self._last_path = "generic" if mdm is None else "fused"
+        if mdm is not None:
+            return self._bpd_fused(mdm, plan_fn, x_start, model_kwargs, noise, seed, first_clip, chunk, return_pred_xstart)
+        device = x_start.device
+        gen = None
+        if noise is None and seed is not None and not x_start.is_cuda:
+            gen = torch.Generator().manual_seed(int(seed))
+        vb, xstart_mse, mse, preds = [], [], [], []
+        for i, t in enumerate(list(range(T))[::-1]):
+            t_batch = torch.tensor([t] * B, device=device)
+            if noise is not None:
+                eps_i = noise[i].to(device)
+            elif seed is not None and x_start.is_cuda:
+                eps_i = engine.seeded_noise(seed, first_clip, list(range(B)), [t] * B, device).view(x_start.shape)
+            elif gen is not None:
+                eps_i = torch.randn(x_start.shape, generator=gen).to(x_start)
+            else:
+                eps_i = torch.randn_like(x_start)
+            x_t = self.q_sample(x_start=x_start, t=t_batch, noise=eps_i)
+            with torch.no_grad():
+                out = self._vb_terms_bpd(model, x_start=x_start, x_t=x_t, t=t_batch, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+            vb.append(out["output"])
+            xstart_mse.append(mean_flat((out["pred_xstart"] - x_start) ** 2))
+            eps = self._predict_eps_from_xstart(x_t, t_batch, out["pred_xstart"])
+            mse.append(mean_flat((eps - eps_i) ** 2))
+            if return_pred_xstart:
+                preds.append(out["pred_xstart"])
+        vb, xstart_mse, mse = torch.stack(vb, dim=1), torch.stack(xstart_mse, dim=1), torch.stack(mse, dim=1)
+        prior_bpd = self._prior_bpd(x_start)
+        res = {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+        if return_pred_xstart:
+            res["pred_xstart"] = torch.stack(preds, 0)
+        return res
+
+    def _bpd_fused(self, mdm, plan_fn, x_start, model_kwargs, noise, seed, first_clip, chunk, want_pred):
+        """All (clip, timestep) pairs in the reference's loop order - pair p = i N + b is iteration i (t = T - 1 - i), clip b - chunk by
+        chunk on the device; the [3][N T] result is read once."""
+        dev, T, B = x_start.device, self.num_timesteps, x_start.shape[0]
+        y = model_kwargs["y"]
+        with torch.no_grad():
+            plan = plan_fn(y)
+            V = len(plan.variants)
+            conds = mdm.variant_conds(y, plan.variants)                       # once for the N clips; gathered per chunk by clip
+            cfg_w = plan.tensor(dev) if V > 1 else None
+            _, tmap = self._model_timesteps(dev)
+            rows = self._cached(("bpd_rows",), lambda: engine.bpd_rows(self.tables()))
+            batch = engine.BpdBatch(mdm, self.q_sample, rows, lambda t: tmap[t], x_start, conds, cfg_w)
+            n_pairs = T * B
+            if noise is None and seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # follows torch.manual_seed
+            flat_noise = None if noise is None else noise.reshape((n_pairs,) + tuple(x_start.shape[1:]))
+            out = torch.empty(3, n_pairs, dtype=torch.float32, device=dev)
+            pred = torch.empty((n_pairs,) + tuple(x_start.shape[1:]), dtype=torch.float32, device=dev) if want_pred else None
+            pairs = torch.arange(n_pairs, device=dev)
+            all_clips, all_steps = pairs % B, (T - 1) - pairs // B
+            for lo, hi in engine.bpd_chunks(n_pairs, V, dev, chunk):
+                if flat_noise is not None:
+                    eps = flat_noise[lo:hi].to(dev, torch.float32).contiguous()
+                else:
+                    eps = engine.seeded_noise(seed, first_clip, [p % B for p in range(lo, hi)], [T - 1 - p // B for p in range(lo, hi)], dev)
+                part = torch.empty(3, hi - lo, dtype=torch.float32, device=dev)
+                got = batch.run(all_clips[lo:hi], all_steps[lo:hi], eps, part, want_pred)
+                out[:, lo:hi].copy_(part)
+                if want_pred:
+                    pred[lo:hi].copy_(got)
+            prior_bpd = self._prior_bpd(x_start.float())
+            batch.finish()
+            vb, xstart_mse, mse = (out[k].view(T, B).t().contiguous() for k in range(3))
+            res = {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+            if want_pred:
+                res["pred_xstart"] = pred.view((T, B) + tuple(x_start.shape[1:]))
+            return res
+
     # What the reference's GaussianDiffusion also defines and none of its trainers, tests or demos reaches (SURVEY.md §2 #1): explicit errors
     # naming the reference lines instead of AttributeError.
     def _unsupported(name, where):
@@ -345,8 +504,7 @@ class GaussianDiffusion:
                                       "not built")
         method.__name__ = name
         return method
-    for _n, _w in (("_vb_terms_bpd", "1201"),
-                   ("_prior_bpd", "1530"), ("calc_bpd_loop", "1548"), ("p_sample_with_grad", "559"), ("ddim_sample_with_grad", "793"),
+    for _n, _w in (("p_sample_with_grad", "559"), ("ddim_sample_with_grad", "793"),
                    ("condition_mean", "427"), ("condition_mean_with_grad", "442"), ("condition_score", "457"), ("condition_score_with_grad", "481")):
         locals()[_n] = _unsupported(_n, _w)
     del _n, _w, _unsupported
@@ -385,7 +543,8 @@ class GaussianDiffusion:
 
     @property
     def last_path(self):
-        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` / `plms_sample_loop` call took (None before the first)."""
+        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` / `plms_sample_loop` / `calc_bpd_loop` call took (None
+        before the first)."""
         return getattr(self, "_last_path", None)
 
     def _fused(self, kind, mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image, step_noise,
