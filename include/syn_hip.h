@@ -211,6 +211,31 @@ typedef struct syn_bpd_row {
 int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
                   const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream);
 
+/* Gradient-guided sampling (diffusion/gaussian_diffusion.py:427-503, 549-605, 765-848; additive, SYN_ABI_VERSION stays 9).  The denoiser is differentiated
+ * with respect to x_t only: x_t enters through h0 = rotary(x_t^T A^T + cond + TE[t]) (A: the folded input chain, 512 x 1536), the eight blocks are
+ * syn_train_stack_fwd / syn_train_stack_bwd, the output Linear and its data gradient syn_linear.
+ * syn_guide_in_fwd: x_bct (n_x, 1536, 1, 32) fp32 -> h0 [32 n_seq][512] fp32 in one launch.  Sequence s reads clip s % n_x (the conditioning variants of
+ * a clip share its latent), row 32 s + f of cond and row t_model[s] of te [n_te][512] (clamped into the table); a_packed = syn_pack_weight of A.
+ * Sequences n_live .. n_seq - 1 are padding: their rows of h0 are zero and nothing is read for them (cond, t_model hold n_live sequences).
+ * syn_guide_in_bwd: the adjoint, dh0 [32 n_seq][512] -> dx_bct (n_seq, 1536, 1, 32) fp32 (inverse rotation, GEMM against at_packed = syn_pack_weight of
+ * A^T [1536][512], channel-major store); accumulate != 0: dx_bct += (a read-modify-write by the element's one owner: no atomics, and the sum over
+ * the variants of a clip, one call after the other on one stream, is bitwise reproducible).  Every pointer 16-byte aligned. */
+int syn_guide_in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const float* cond, const float* te, int32_t n_te, const int32_t* t_model,
+                     const float* rot_cos, const float* rot_sin, int32_t n_live, int32_t n_seq, float* h0, void* stream);
+int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_cos, const float* rot_sin, int32_t n_seq, int32_t accumulate, float* dx_bct,
+                     void* stream);
+/* The update behind cond_fn's gradient `grad`, element-wise on (n_clips, 1536, 1, 32) fp32; clip b takes row t_idx[b] of coef [n_rows][8] (an index
+ * outside the table: NaN in that clip's output, nothing read for it):
+ *   mode 0 (condition_mean, p_sample)    row {variance, exp(0.5 log_variance)}; a = the posterior mean:
+ *          out = a + variance grad + [t != 0] sigma noise
+ *   mode 1 (condition_score, ddim_sample) row {sqrt(1 - ab), sqrt(1 / ab), sqrt(1 / ab - 1), sqrt(ab_prev), sqrt(1 - ab_prev - sigma^2), sigma}; a = x_t:
+ *          eps = (r a - pred_x0) / m - sqrt(1 - ab) grad;  x0' = r a - m eps;  eps' = (r a - x0') / m;  out = x0' sqrt(ab_prev) + dir eps' + [t != 0] sigma noise
+ * noise: (n_clips, 1536, 1, 32), or NULL and draw != 0: element (b, channel c, frame f) is element ((first_clip + b) 32 + f) 1536 + c of
+ * syn_randn(seed, stream_id = t_idx[b]) - bitwise the step kernels' draw; NULL and draw == 0: no noise.  Clips with t_idx == 0 or sigma == 0 neither read
+ * nor draw.  pred_x0 is left as it is (the reference returns the unguided one, :557, :791, :848). */
+int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
+                     uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

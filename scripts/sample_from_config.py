@@ -8,6 +8,7 @@ Fréchet statistic of the sampled latents against reference statistics.
                                          [--random-init] [--inputs in.npz] [--ref-stats ref.npz] [--out out.npz]
                                          [--upper-prompt TEXT] [--hands-prompt TEXT] [--lower-prompt TEXT]
                                          [--keep-from TAKE.npz [--keep-parts upper,hands,lower] [--keep-frames a:b]]
+                                         [--guide-from TAKE.npz [--guide-parts upper,hands,lower] [--guide-frames a:b] [--guide-scale S]]
 
 --plms          the pseudo linear multistep sampler (`plms_sample_loop`) over the 50-step respacing, at order K = 2 (default), 3 or 4.
 --random-init   ignore the checkpoint / statistics paths of the YAML and use the name-keyed synthetic weights (there is no
@@ -27,6 +28,11 @@ Fréchet statistic of the sampled latents against reference statistics.
                 counts per part but are not guaranteed to be its joints.  It goes through `poses.encode_take` to the sampler's
                 latents; the body parts named by --keep-parts (all frames) and the latent frames a:b (half-open, pose frame / 4; all channels)
                 are kept from it and the rest is generated.
+--guide-from / --guide-parts / --guide-frames / --guide-scale
+                the soft counterpart (gradient guidance, `guided.keyframe_cond_fn` with cond_fn_with_grad=True; BEAT-X configuration): the same kind
+                of take and the same selection, but the chosen parts / frames are PULLED towards the take with log p = -S sum keep (pred_xstart -
+                take)^2 (default S = 0.05) instead of copied, and every entry stays generated.  One window (the take's first `pose_length` pose
+                frames): guidance over windows is not built into `longform.sample_long`.
 """
 import argparse
 import json
@@ -56,15 +62,16 @@ def prompt_styles(args, prompts: dict, dev, random_init: bool) -> dict:
         return {f"{part}_mask": (None if prompts[part] is None else text(prompts[part]).loc) for part in PROMPT_PARTS}
 
 
-def edit_from_take(a, args, s, dev, n: int, batch: int, squeeze: int):
-    """(known_latent, keep) of --keep-from / --keep-parts / --keep-frames for `sample_long(edit=...)`."""
+def edit_from_take(a, args, s, dev, n: int, batch: int, squeeze: int, flag: str = "keep"):
+    """(known_latent, keep) of --keep-from / --keep-parts / --keep-frames for `sample_long(edit=...)` (flag "guide": of --guide-from / ...)."""
     from syntalker_amd import poses
     if config.is_h3d(args):
-        raise SystemExit("--keep-from takes 165-channel SMPL-X poses: the BEAT-X configuration")
-    z = np.load(a.keep_from)
+        raise SystemExit(f"--{flag}-from takes 165-channel SMPL-X poses: the BEAT-X configuration")
+    path, parts_arg, frames_arg = (getattr(a, f"{flag}_{k}") for k in ("from", "parts", "frames"))
+    z = np.load(path)
     pose = torch.from_numpy(z["pose"]).float().to(dev)
     if pose.shape[0] != batch or pose.shape[1] < n:
-        raise SystemExit(f"--keep-from: pose is {tuple(pose.shape)}, the run has {batch} takes of {n} pose frames")
+        raise SystemExit(f"--{flag}-from: pose is {tuple(pose.shape)}, the run has {batch} takes of {n} pose frames")
     pose = pose[:, :n - n % squeeze]
     trans_v = None
     if s.use_trans:
@@ -74,10 +81,10 @@ def edit_from_take(a, args, s, dev, n: int, batch: int, squeeze: int):
     stats = None if s.trans_mean is None else (s.trans_mean, s.trans_std)
     with torch.no_grad():
         known = poses.encode_take(pose, trans_v, s.vq["upper"], s.vq["hands"], s.vq["lower"], masks, None, stats, s.latent_scale)["latent_in"]
-    parts = tuple(p for p in (a.keep_parts or "").split(",") if p)
+    parts = tuple(p for p in (parts_arg or "").split(",") if p)
     frames = None
-    if a.keep_frames:
-        lo, hi = a.keep_frames.split(":")
+    if frames_arg:
+        lo, hi = frames_arg.split(":")
         frames = (int(lo or 0), int(hi) if hi else known.shape[1])
     return known, longform.keep_mask(known.shape[1], parts, frames)
 
@@ -100,7 +107,17 @@ def main(argv=None) -> dict:
     ap.add_argument("--keep-from")
     ap.add_argument("--keep-parts")
     ap.add_argument("--keep-frames")
+    ap.add_argument("--guide-from")
+    ap.add_argument("--guide-parts")
+    ap.add_argument("--guide-frames")
+    ap.add_argument("--guide-scale", type=float, default=0.05)
     a = ap.parse_args(argv)
+    if (a.guide_parts or a.guide_frames) and not a.guide_from:
+        raise SystemExit("--guide-parts / --guide-frames need --guide-from: the take to pull them towards")
+    if a.guide_from and not (a.guide_parts or a.guide_frames):
+        raise SystemExit("--guide-from needs --guide-parts and / or --guide-frames: what to pull towards the take")
+    if a.guide_from and (a.keep_from or a.plms):
+        raise SystemExit("--guide-from goes with neither --keep-from nor --plms (the PLMS loop takes no cond_fn)")
     if (a.keep_parts or a.keep_frames) and not a.keep_from:
         raise SystemExit("--keep-parts / --keep-frames need --keep-from: the take to keep them from")
     if a.keep_from and not (a.keep_parts or a.keep_frames):
@@ -139,10 +156,24 @@ def main(argv=None) -> dict:
         model = TwoClassifierFreeSampleModel_Bodypart(s.model)
         y_extra = {"style_feature": prompt_styles(args, prompts, dev, a.random_init)}
     edit = edit_from_take(a, args, s, dev, n, word.shape[0], squeeze) if a.keep_from else None
+    guide = edit_from_take(a, args, s, dev, n, word.shape[0], squeeze, "guide") if a.guide_from else None
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    lat = longform.sample_long(diffusion, model, audio, word, seed_lat, n, pose_length=pose_length, pre_frames=pre, squeeze=squeeze,
-                               use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra, edit=edit,
-                               **({"sampler": "plms", "plms_order": a.plms_order} if a.plms else {}))
+    if guide is not None:
+        # one window under gradient guidance: the selection of the take as a soft objective on pred_xstart
+        from syntalker_amd import guided
+        round_l = longform.window_plan(n, pose_length, pre, squeeze)[0]
+        target, keep = longform.window_edit(0, guide[0], guide[1].to(dev), round_l, pose_length // squeeze, squeeze)
+        y = longform.window_inputs(0, audio, word, seed_lat, None, round_l, pre, squeeze, style_dim, y_extra)
+        loop = diffusion.ddim_sample_loop if a.ddim else diffusion.p_sample_loop
+        shape = (word.shape[0], 1536, 1, pose_length // squeeze)
+        x_T = torch.randn(*shape, generator=torch.Generator().manual_seed(a.seed)).to(dev)      # (the whole run follows --seed)
+        x = loop(model, shape, noise=x_T, clip_denoised=False, cond_fn=guided.keyframe_cond_fn(target, keep, a.guide_scale, True),
+                 cond_fn_with_grad=True, model_kwargs={"y": y}, seed=a.seed)
+        lat, rounds = x[:, :, 0, :].permute(0, 2, 1).contiguous(), 1
+    else:
+        lat = longform.sample_long(diffusion, model, audio, word, seed_lat, n, pose_length=pose_length, pre_frames=pre, squeeze=squeeze,
+                                   use_ddim=a.ddim, seed=a.seed, style_dim=style_dim, y_extra=y_extra, edit=edit,
+                                   **({"sampler": "plms", "plms_order": a.plms_order} if a.plms else {}))
     torch.cuda.synchronize(); t1 = time.perf_counter()
     out = longform.decode_take(lat, s.vq["upper"], s.vq["hands"], s.vq["lower"], s.latent_scale, use_trans=s.use_trans,
                                trans_mean=s.trans_mean, trans_std=s.trans_std)
@@ -156,6 +187,10 @@ def main(argv=None) -> dict:
         kept = edit[1].to(lat.device)[:lat.shape[1]].expand(lat.shape)
         rep["edit"] = {"path": diffusion.last_path, "kept_fraction": round(float(kept.float().mean()), 4),
                        "kept_exact": bool(torch.equal(lat[kept], edit[0][:, :lat.shape[1]][kept]))}
+    if guide is not None:
+        w = keep[:, :, 0, :].permute(0, 2, 1).float()
+        dist = lambda v: float((w * (v - target[:, :, 0, :].permute(0, 2, 1))).norm() / (w * target[:, :, 0, :].permute(0, 2, 1)).norm().clamp_min(1e-30))
+        rep["guide"] = {"path": diffusion.last_path, "scale": a.guide_scale, "guided_fraction": round(float(w.mean()), 4), "rel_distance_to_take": round(dist(lat), 4)}
     if a.ref_stats:
         z = np.load(a.ref_stats)
         emb = metrics.latent_embedding(lat.float().cpu().numpy(), dim=int(z["mu"].shape[0]))

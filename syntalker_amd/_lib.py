@@ -30,7 +30,8 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text",
            "syn_vq_train_pack", "syn_vq_train_cast", "syn_vq_train_ew", "syn_vq_train_pairsum", "syn_vq_train_stuff", "syn_vq_train_wgrad",
            "syn_vq_train_codebook_prep", "syn_vq_train_tile", "syn_vq_train_quantize", "syn_vq_train_codebook_update",
-           "syn_vq_train_loss_parts", "syn_vq_train_loss", "syn_vq_train_scalars", "syn_plms_update", "syn_bpd_terms")
+           "syn_vq_train_loss_parts", "syn_vq_train_loss", "syn_vq_train_scalars", "syn_plms_update", "syn_bpd_terms",
+           "syn_guide_in_fwd", "syn_guide_in_bwd", "syn_guide_update")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -357,6 +358,9 @@ def load():
     lib.syn_vq_train_scalars.argtypes = [vp, i32, i64, vp, i32, vp, i32, i32, f32, vp, vp]
     lib.syn_plms_update.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
     lib.syn_bpd_terms.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
+    lib.syn_guide_in_fwd.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
+    lib.syn_guide_in_bwd.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.syn_guide_update.argtypes = [i32, vp, vp, vp, vp, i32, u64, u64, vp, i32, vp, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes",

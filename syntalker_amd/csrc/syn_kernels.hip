@@ -265,23 +265,62 @@ __device__ __forceinline__ void gemm_mainloop(f32x4 (&acc)[NF][MT / 16], const _
 #define SYN_GEMM_RING 12
 #endif
 constexpr int kResidentMaxK = 2048;
+// The resident loop in two pieces, so that a kernel with a loader of its own (csrc/syn_guide.inc) runs the same K loop: `staged_prime` issues the first
+// R - 1 k-steps of weight fragments (before the activation block is staged: the two overlap), `staged_loop` is the barrier-free loop over an LDS image
+// [K tile][row 0..MT-1][8 slots of 16 B, slot ^ (row & 7)] that is complete and visible (a barrier lies between).  SWAP: the activation fragment is
+// the A operand - acc[nf][mf][r] = out[m = 16 mf + 4 (l >> 4) + r][n = 16 nf + (l & 15)] instead of out[m = 16 mf + (l & 15)][n = 16 nf + 4 (l >> 4) + r].
+template <int NF, int R>
+__device__ __forceinline__ void staged_w_load(uint4 (&wr)[NF], const uint4* __restrict__ Wq, int KS, int kstep) {
+    if (kstep < KS) {
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf) wr[nf] = Wq[((size_t)nf * KS + kstep) * 64];
+    }
+}
+template <int NF, int R>
+__device__ __forceinline__ void staged_prime(uint4 (&w)[R][NF], const uint4* __restrict__ Wq, int KS) {
+    static_assert(R % 2 == 0 && (R - 1) * NF <= 63, "even ring (the k-step's half of its K tile is static), vmcnt has 6 bits");
+#pragma unroll
+    for (int s = 0; s < R - 1; ++s) staged_w_load<NF, R>(w[s], Wq, KS, s);
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int MT, int NF, int R, bool SWAP = false>
+__device__ __forceinline__ void staged_loop(f32x4 (&acc)[NF][MT / 16], uint4 (&w)[R][NF], int KS, const uint4* __restrict__ Wq, const char* smem) {
+    constexpr int MF = MT / 16, TILE = MT * 128;
+    const int lane = threadIdx.x & 63;
+    int xoff[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) xoff[h] = (lane & 15) * 128 + ((((4 * h) + (lane >> 4)) ^ (lane & 7)) << 4);
+    for (int base = 0; base < KS; base += R) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int ks = base + i;
+            staged_w_load<NF, R>(w[(i + R - 1) % R], Wq, KS, ks + R - 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks < KS) {
+                bf16x8 xf[MF];
+#pragma unroll
+                for (int mf = 0; mf < MF; ++mf) xf[mf] = *reinterpret_cast<const bf16x8*>(smem + (ks >> 1) * TILE + mf * 2048 + xoff[i & 1]);
+#pragma unroll
+                for (int nf = 0; nf < NF; ++nf)
+#pragma unroll
+                    for (int mf = 0; mf < MF; ++mf) {
+                        const bf16x8 wf = __builtin_bit_cast(bf16x8, w[i][nf]);
+                        acc[nf][mf] = SWAP ? MFMA16(xf[mf], wf, acc[nf][mf]) : MFMA16(wf, xf[mf], acc[nf][mf]);
+                    }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 template <int MT, int NF, int R>
 __device__ __forceinline__ void gemm_mainloop_resident(f32x4 (&acc)[NF][MT / 16], const __bf16* __restrict__ X, int ldx, int x_rows, int m0, int M,
                                                        int K, const uint4* __restrict__ Wq, char* smem) {
-    static_assert(R % 2 == 0 && (R - 1) * NF <= 63, "even ring (the k-step's half of its K tile is static), vmcnt has 6 bits");
-    constexpr int MF = MT / 16, TILE = MT * 128;
-    const int tid = threadIdx.x, lane = tid & 63;
+    constexpr int TILE = MT * 128;
+    const int tid = threadIdx.x;
     const int KS = K / 32, total = (K / kKT) * MT * 8;       // 16-byte chunks of the block: [K tile][row 0..MT-1][slot 0..7]
     uint4 w[R][NF];
-    auto w_load = [&](uint4 (&wr)[NF], int kstep) {
-        if (kstep < KS) {
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) wr[nf] = Wq[((size_t)nf * KS + kstep) * 64];
-        }
-    };
-#pragma unroll
-    for (int s = 0; s < R - 1; ++s) w_load(w[s], s);
-    __builtin_amdgcn_sched_barrier(0);
+    staged_prime<NF, R>(w, Wq, KS);
     for (int base = 0; base < total; base += 4 * kThreads) {
         uint4 st[4];
 #pragma unroll
@@ -296,28 +335,8 @@ __device__ __forceinline__ void gemm_mainloop_resident(f32x4 (&acc)[NF][MT / 16]
             if (idx < total) *reinterpret_cast<uint4*>(smem + (idx / (MT * 8)) * TILE + row * 128 + ((slot ^ (row & 7)) << 4)) = st[i];
         }
     }
-    int xoff[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) xoff[h] = (lane & 15) * 128 + ((((4 * h) + (lane >> 4)) ^ (lane & 7)) << 4);
     __syncthreads();
-    for (int base = 0; base < KS; base += R) {
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const int ks = base + i;
-            w_load(w[(i + R - 1) % R], ks + R - 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks < KS) {
-                bf16x8 xf[MF];
-#pragma unroll
-                for (int mf = 0; mf < MF; ++mf) xf[mf] = *reinterpret_cast<const bf16x8*>(smem + (ks >> 1) * TILE + mf * 2048 + xoff[i & 1]);
-#pragma unroll
-                for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-                    for (int mf = 0; mf < MF; ++mf) acc[nf][mf] = MFMA16(__builtin_bit_cast(bf16x8, w[i][nf]), xf[mf], acc[nf][mf]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    staged_loop<MT, NF, R>(acc, w, KS, Wq, smem);
 }
 
 // Row mean / rstd over the 512 columns a workgroup owns (8 waves x 64).  One pass (sum and sum of squares,
@@ -1753,6 +1772,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_t2m.inc"
 #include "syn_plms.inc"
 #include "syn_bpd.inc"
+#include "syn_guide.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2256,6 +2276,21 @@ int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* co
 int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
                   const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream) {
     return bpd::terms(table, n_rows, t_row, clip, x_start, n_clips, x_t, noise, pred_x0, n_seq, out, stream);
+}
+
+int syn_guide_in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const float* cond, const float* te, int32_t n_te, const int32_t* t_model,
+                     const float* rot_cos, const float* rot_sin, int32_t n_live, int32_t n_seq, float* h0, void* stream) {
+    return guide::in_fwd(x_bct, n_x, a_packed, cond, te, n_te, t_model, rot_cos, rot_sin, n_live, n_seq, h0, stream);
+}
+
+int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_cos, const float* rot_sin, int32_t n_seq, int32_t accumulate, float* dx_bct,
+                     void* stream) {
+    return guide::in_bwd(dh0, at_packed, rot_cos, rot_sin, n_seq, accumulate, dx_bct, stream);
+}
+
+int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
+                     uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream) {
+    return guide::update(mode, a, pred_x0, grad, noise, draw, seed, first_clip, coef, n_rows, t_idx, n_clips, out, stream);
 }
 
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {

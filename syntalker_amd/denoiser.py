@@ -221,8 +221,8 @@ class MDM(nn.Module):
             from . import training                      # differentiable path: HIP GEMMs fwd/dgrad/wgrad (training.py)
             return training.train_forward(self, x, timesteps, y, drop_path=self.drop_path)
         if torch.is_grad_enabled() and x.requires_grad:
-            raise RuntimeError("MDM.eval() runs the fused inference kernels, which are not differentiable: the output would be "
-                               "detached from x.  Set model.differentiable_eval = True (or call .train()) for gradients.")
+            from . import guided                        # frozen weights, gradient with respect to x only (gradient-guided sampling)
+            return guided.forward(self, x, timesteps, y)
         return self.forward_variants(x, timesteps, y, [self.own_variant(y)], None)
 
     def forward_variants(self, x, timesteps, y, variants, weights):
@@ -235,6 +235,11 @@ class MDM(nn.Module):
         if Cc != engine.CH or Tt != engine.T:
             raise SynHipError(f"step kernels are specialised for (B,1536,1,32) latents, got {tuple(x.shape)}")
         V = len(variants)
+        if torch.is_grad_enabled() and x.requires_grad:           # (eval mode, under a guidance wrapper: the node that is differentiable in x)
+            from . import guided
+            with torch.no_grad():
+                conds = self.variant_conds(y, variants)
+            return guided.denoise(self, x, timesteps, conds, None if V == 1 else weights.to(x.device))
         pm = self.packed()
         sb = self.step_buffers(B, V)
         with torch.no_grad():

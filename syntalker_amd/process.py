@@ -14,6 +14,9 @@ What is different underneath:
     ``p_sample_loop`` / ``ddim_sample_loop`` / ``plms_sample_loop`` run the FUSED loop: conditioning hoisted out of the loop,
     x kept token-major on the device, one hipGraph replay per step with the posterior / DDIM update
     fused into the output GEMM's epilogue (engine.py, csrc/syn_kernels.hip);
+  * with ``cond_fn`` / ``cond_fn_with_grad`` (gradient guidance, gaussian_diffusion.py:427-503, 549-605, 765-848) the loops run eagerly on the
+    same model: a node that is differentiable in x_t, the user's function, one update kernel per step (guided.py); the single-step methods
+    ``p_sample[_with_grad]``, ``ddim_sample[_with_grad]`` and ``condition_mean / condition_score[_with_grad]`` take any model;
   * any other model goes through the generic per-step path (same arithmetic in torch ops).
 Only the configuration the reference's factory builds is implemented (START_X, FIXED_SMALL, MSE);
 other enum values raise NotImplementedError.
@@ -293,29 +296,31 @@ class GaussianDiffusion:
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                  const_noise=False, *, noise=None):
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn (classifier guidance) is never used by the reference's callers")
         out = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
         if noise is None:
             noise = torch.randn_like(x)
         if const_noise:
             noise = noise[[0]].repeat(x.shape[0], 1, 1, 1)
+        if cond_fn is not None:
+            out["mean"] = self.condition_mean(cond_fn, out, x, t, model_kwargs=model_kwargs)
         sample = out["mean"] + self._nonzero(t, x) * torch.exp(0.5 * out["log_variance"]) * noise
         return {"sample": sample, "pred_xstart": out["pred_xstart"]}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                     eta=0.0, *, noise=None):
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn (classifier guidance) is never used by the reference's callers")
-        out = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
-        x0 = out["pred_xstart"]
+        out_orig = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+        out = out_orig if cond_fn is None else self.condition_score(cond_fn, out_orig, x, t, model_kwargs=model_kwargs)
+        return self._ddim_update(out["pred_xstart"], out_orig["pred_xstart"], x, t, eta, noise)
+
+    def _ddim_update(self, x0, x0_orig, x, t, eta, noise):
+        """gaussian_diffusion.py:770-791: the DDIM step from a (possibly guided) pred_xstart; the returned pred_xstart is the unguided one."""
         eps = (self._tab("sqrt_recip_alphas_cumprod", t, x) * x - x0) / self._tab("sqrt_recipm1_alphas_cumprod", t, x)
         ab, abp = self._tab("alphas_cumprod", t, x), self._tab("alphas_cumprod_prev", t, x)
         sigma = eta * torch.sqrt((1 - abp) / (1 - ab)) * torch.sqrt(1 - ab / abp)
         if noise is None:
             noise = torch.randn_like(x)
         mean = x0 * torch.sqrt(abp) + torch.sqrt(1 - abp - sigma ** 2) * eps
-        return {"sample": mean + self._nonzero(t, x) * sigma * noise, "pred_xstart": x0}
+        return {"sample": mean + self._nonzero(t, x) * sigma * noise, "pred_xstart": x0_orig}
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
         """gaussian_diffusion.py:850-886: x_{t+1} by the deterministic DDIM ODE run backwards (generic path: one model call)."""
@@ -495,19 +500,63 @@ class GaussianDiffusion:
                 res["pred_xstart"] = pred.view((T, B) + tuple(x_start.shape[1:]))
             return res
 
-    # What the reference's GaussianDiffusion also defines and none of its trainers, tests or demos reaches: explicit errors
-    # naming the reference lines instead of AttributeError.
-    def _unsupported(name, where):
-        def method(self, *a, **k):
-            raise NotImplementedError(f"GaussianDiffusion.{name} (reference diffusion/gaussian_diffusion.py:{where}) is not on the path any of the "
-                                      "reference's callers takes (train.py / test.py / demo.py use p_sample_loop, ddim_sample_loop, training_losses); "
-                                      "not built")
-        method.__name__ = name
-        return method
-    for _n, _w in (("p_sample_with_grad", "559"), ("ddim_sample_with_grad", "793"),
-                   ("condition_mean", "427"), ("condition_mean_with_grad", "442"), ("condition_score", "457"), ("condition_score_with_grad", "481")):
-        locals()[_n] = _unsupported(_n, _w)
-    del _n, _w, _unsupported
+    # ---- gradient guidance (gaussian_diffusion.py:427-503, 559-605, 793-848): any model, plain torch arithmetic under autograd ---------------
+    # Until they were built every call of these raised NotImplementedError naming the reference line; a call that does not bind still does
+    # (`UnboundCall`).  cond_fn returns grad(log p(y | x)) with respect to x; the `_with_grad` forms hand it the p_mean_variance dict, computed
+    # under autograd from an x that requires grad, so that it can differentiate through pred_xstart.
+    @_names_reference_line("427")
+    def condition_mean(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """gaussian_diffusion.py:427-440 (Sohl-Dickstein et al. 2015): mean + variance * cond_fn(x, t).  Under a respaced process cond_fn
+        sees the base process's timesteps (respace.py:99-100)."""
+        gradient = self._wrap_model(cond_fn)(x, self._scale_timesteps(t), **(model_kwargs or {}))
+        return p_mean_var["mean"].float() + p_mean_var["variance"] * gradient.float()
+
+    @_names_reference_line("442")
+    def condition_mean_with_grad(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """gaussian_diffusion.py:442-455: cond_fn(x, t, p_mean_var) with the process's own timestep indices (the reference does not map them)."""
+        gradient = cond_fn(x, t, p_mean_var, **(model_kwargs or {}))
+        return p_mean_var["mean"].float() + p_mean_var["variance"] * gradient.float()
+
+    def _score_from(self, gradient, p_mean_var, x, t):
+        eps = self._predict_eps_from_xstart(x, t, p_mean_var["pred_xstart"])
+        eps = eps - (1 - self._tab("alphas_cumprod", t, x)).sqrt() * gradient
+        out = p_mean_var.copy()
+        out["pred_xstart"] = self._predict_xstart_from_eps(x, t, eps)
+        out["mean"], _, _ = self.q_posterior_mean_variance(x_start=out["pred_xstart"], x_t=x, t=t)
+        return out
+
+    @_names_reference_line("457")
+    def condition_score(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """gaussian_diffusion.py:457-479 (Song et al. 2020): eps - sqrt(1 - alpha_bar) cond_fn(x, t), pred_xstart and mean re-derived."""
+        return self._score_from(self._wrap_model(cond_fn)(x, self._scale_timesteps(t), **(model_kwargs or {})), p_mean_var, x, t)
+
+    @_names_reference_line("481")
+    def condition_score_with_grad(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """gaussian_diffusion.py:481-503."""
+        return self._score_from(cond_fn(x, t, p_mean_var, **(model_kwargs or {})), p_mean_var, x, t)
+
+    @_names_reference_line("559")
+    def p_sample_with_grad(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, *, noise=None):
+        """gaussian_diffusion.py:559-605: p_sample with p_mean_variance evaluated under autograd on a detached x that requires grad."""
+        with torch.enable_grad():
+            x = x.detach().requires_grad_()
+            out = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+            if noise is None:
+                noise = torch.randn_like(x)
+            if cond_fn is not None:
+                out["mean"] = self.condition_mean_with_grad(cond_fn, out, x, t, model_kwargs=model_kwargs)
+        sample = out["mean"] + self._nonzero(t, x) * torch.exp(0.5 * out["log_variance"]) * noise
+        return {"sample": sample, "pred_xstart": out["pred_xstart"].detach()}
+
+    @_names_reference_line("793")
+    def ddim_sample_with_grad(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, *, noise=None):
+        """gaussian_diffusion.py:793-848."""
+        with torch.enable_grad():
+            x = x.detach().requires_grad_()
+            out_orig = self.p_mean_variance(model, x, t, clip_denoised, denoised_fn, model_kwargs)
+            out = out_orig if cond_fn is None else self.condition_score_with_grad(cond_fn, out_orig, x, t, model_kwargs=model_kwargs)
+        res = self._ddim_update(out["pred_xstart"].detach(), out_orig["pred_xstart"].detach(), x, t, eta, noise)
+        return res
 
     # ---- loops ---------------------------------------------------------------------------------------
     def _start(self, shape, noise, device, skip_timesteps, init_image):
@@ -543,7 +592,7 @@ class GaussianDiffusion:
 
     @property
     def last_path(self):
-        """"fused" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` / `plms_sample_loop` / `calc_bpd_loop` call took (None
+        """"fused", "guided" or "generic": the path the last `p_sample_loop` / `ddim_sample_loop` / `plms_sample_loop` / `calc_bpd_loop` call took (None
         before the first)."""
         return getattr(self, "_last_path", None)
 
@@ -688,14 +737,45 @@ class GaussianDiffusion:
             yield out
             img = out["sample"]
 
+    def _guidable(self, model, model_kwargs, shape, const_noise):
+        """The model a guided loop runs on: a HIP `MDM` in eval mode on the GPU (possibly under guidance wrappers), (B, 1536, 1, 32) latents."""
+        mdm, plan_fn = resolve(model)
+        y = (model_kwargs or {}).get("y")
+        if mdm is None or mdm.training or const_noise or y is None or tuple(shape[1:]) != (engine.CH, 1, engine.T):
+            return None, None
+        if not next(mdm.parameters()).is_cuda:
+            return None, None
+        return mdm, plan_fn
+
+    def _loop_steps(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
+                    randomize_class, cond_fn_with_grad, const_noise, eta, step_noise, seed, first_clip):
+        """The steps of `p_sample_loop_progressive` / `ddim_sample_loop_progressive`.  cond_fn / cond_fn_with_grad: the guided loop
+        (`guided.sample_loop`) when the model resolves to a HIP `MDM` in eval mode on the GPU; for any other model the loops refuse them up
+        front, as they always have (the single-step methods take cond_fn for any model)."""
+        if randomize_class:
+            raise NotImplementedError("randomize_class is never used by the reference's callers")
+        if cond_fn is not None or cond_fn_with_grad:
+            mdm, plan_fn = self._guidable(model, model_kwargs, shape, const_noise)
+            if mdm is None or cond_fn is None:
+                raise NotImplementedError("cond_fn / cond_fn_with_grad (gradient guidance) in a sampling loop run on a HIP MDM in eval() mode on the GPU "
+                                          "with (B, 1536, 1, 32) latents; for other models call p_sample / ddim_sample[_with_grad] step by step")
+            from . import guided
+            self._last_path = "guided"
+            yield from guided.sample_loop(self, kind, mdm, plan_fn, shape, noise, clip_denoised, denoised_fn, cond_fn, bool(cond_fn_with_grad),
+                                          model_kwargs, eta, skip_timesteps, init_image, step_noise, seed, first_clip, progress)
+            return
+        if kind == "ddpm":
+            yield from self._generic(self.p_sample, model, shape, noise, model_kwargs, device, progress, skip_timesteps,
+                                     init_image, step_noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, const_noise=const_noise)
+        else:
+            yield from self._generic(self.ddim_sample, model, shape, noise, model_kwargs, device, progress, skip_timesteps,
+                                     init_image, step_noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, eta=eta)
+
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
                                   randomize_class=False, cond_fn_with_grad=False, const_noise=False, *, step_noise=None):
-        if randomize_class or cond_fn_with_grad:
-            raise NotImplementedError("randomize_class / cond_fn_with_grad are never used by the reference's callers")
-        yield from self._generic(self.p_sample, model, shape, noise, model_kwargs, device, progress, skip_timesteps,
-                                 init_image, step_noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                 cond_fn=cond_fn, const_noise=const_noise)
+        yield from self._loop_steps("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+                                    init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0, step_noise, None, 0)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -716,9 +796,9 @@ class GaussianDiffusion:
                                 step_noise, seed, progress, each, first_clip)
             return dump if dump_steps is not None else final
         final, dump = None, []
-        for i, out in enumerate(self.p_sample_loop_progressive(
-                model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
-                init_image, randomize_class, cond_fn_with_grad, const_noise, step_noise=step_noise)):
+        for i, out in enumerate(self._loop_steps("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
+                                                 skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0, step_noise,
+                                                 seed, first_clip)):
             if dump_steps is not None and i in dump_steps:
                 dump.append(out["sample"].clone())
             final = out
@@ -727,11 +807,8 @@ class GaussianDiffusion:
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0,
                                      init_image=None, randomize_class=False, cond_fn_with_grad=False, *, step_noise=None):
-        if randomize_class or cond_fn_with_grad:
-            raise NotImplementedError("randomize_class / cond_fn_with_grad are never used by the reference's callers")
-        yield from self._generic(self.ddim_sample, model, shape, noise, model_kwargs, device, progress, skip_timesteps,
-                                 init_image, step_noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                 cond_fn=cond_fn, eta=eta)
+        yield from self._loop_steps("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+                                    init_image, randomize_class, cond_fn_with_grad, False, eta, step_noise, None, 0)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
@@ -747,9 +824,8 @@ class GaussianDiffusion:
             return self._fused("ddim", mdm, plan_fn, shape, noise, model_kwargs, eta, skip_timesteps, init_image,
                                step_noise, seed, progress, None, first_clip)
         final = None
-        for out in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                     model_kwargs, device, progress, eta, skip_timesteps, init_image,
-                                                     randomize_class, cond_fn_with_grad, step_noise=step_noise):
+        for out in self._loop_steps("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+                                    init_image, randomize_class, cond_fn_with_grad, False, eta, step_noise, seed, first_clip):
             final = out
         return final["sample"]
 
