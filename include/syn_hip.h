@@ -236,6 +236,46 @@ int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_c
 int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
                      uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream);
 
+/* Motion metrics behind the sampler (the reference's test(), diffusion_rvqvae_trainer.py:626-684, 722-728; utils/metric.py; utils/plot_script.py:15-52;
+ * additive, SYN_ABI_VERSION stays 9; csrc/syn_joints.inc).  fp32 device tensors unless noted; deterministic, no floating-point atomics; every call
+ * enqueues on `stream`, allocates nothing and is graph-capturable.
+ *
+ * syn_fk_joints: forward kinematics of a tree of n_joints <= 64 joints.  parents [n_joints] int32, every parent an EARLIER joint, roots -1 (an entry
+ * that is not an earlier joint is taken as a root); rest_joints (n_takes, n_joints, 3); rot (n_frames, n_joints, 3) axis-angle (rot6d == 0: Rodrigues,
+ * exact at 0) or (n_frames, n_joints, 6) (rot6d != 0: the Gram-Schmidt of syn_rot6d_to_axis_angle's first half); transl (n_frames, 3) or NULL.  Frame n
+ * belongs to take take_of_frame[n], or to take n / frames_per_take where take_of_frame is NULL; a take outside [0, n_takes) gives NaN joints.
+ * pose_mean [n_joints][3] or NULL: added to the axis-angle vectors before Rodrigues - SMPL-X's `full_pose += pose_mean`, i.e. the hands' mean pose of a
+ * model built with flat_hand_mean = False, as the reference builds it (axis-angle input only: refused with rot6d != 0).
+ * joints_out (n_frames, n_joints, 3): G_j = G_parent . [R_j | rest_j - rest_parent], the root at rest_0 (+ transl). */
+int syn_fk_joints(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* rot, int32_t rot6d, const float* transl,
+                  const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, const float* pose_mean, float* joints_out, void* stream);
+/* joints_in (n_takes, n_frames >= 2, n_joints, 3) -> speed (n_takes, n_frames, n_joints): forward / central / backward differences times fps within each
+ * take, Euclidean norm per joint, divided by mmae [n_joints] where it is not NULL (metric.py:98-109). */
+int syn_joint_speed(const float* joints_in, int32_t n_takes, int32_t n_frames, int32_t n_joints, float fps, const float* mmae, float* speed, void* stream);
+/* vel (n_takes, n_frames, n_joints) -> mask (n_takes, t_end - t_start, n_joints) uint8, 0 <= t_start <= t_end <= n_frames: slice index j of joint i is a
+ * beat where vel[t_start + j, i] is strictly below its `order` neighbours on either side (indices clipped to the slice: argrelextrema's mode 'clip')
+ * AND vel[j, i] > threshold - frame j of the whole take, as the reference has it (metric.py:111-127). */
+int syn_motion_beats(const float* vel, int32_t n_takes, int32_t n_frames, int32_t n_joints, int32_t t_start, int32_t t_end, int32_t order, float threshold,
+                     uint8_t* mask, void* stream);
+/* Beat consistency (metric.py:205-241).  mask as above (n_slice <= 16000: n_slice / 2 + 1 doubles of LDS per workgroup); upper_body [n_upper] int32 joint indices; onsets: fp64 seconds, take k's are
+ * onsets[onset_offsets[k] .. onset_offsets[k + 1]) (at least one per take: the host's to check).  per_joint (n_takes, n_upper): the mean over a take's
+ * onsets of exp(-d^2 / 2 sigma^2), d the distance to the joint's nearest beat time j / pose_fps (0 for a joint without beats); bc [n_takes]: the mean
+ * over the joints. */
+int syn_beat_align(const uint8_t* mask, int32_t n_takes, int32_t n_slice, int32_t n_joints, const int32_t* upper_body, int32_t n_upper, const double* onsets,
+                   const int32_t* onset_offsets, double pose_fps, float sigma, float* per_joint, float* bc, void* stream);
+/* L1 diversity (metric.py:12-27): out[k] (fp64) = sum over take k of x (n_takes, n, channels) of |x - the take's mean over its rows|; x is only read.
+ * fp64 sums in an order fixed by (n, channels) alone: bitwise the same on every run, for every `blocks` (the grid of the two passes; 0 = the library's
+ * choice) and whichever takes share the call.  workspace: syn_l1div_workspace_bytes(n_takes, n, channels) bytes (-1 for counts
+ * below 1), 8-byte aligned. */
+int64_t syn_l1div_workspace_bytes(int32_t n_takes, int64_t n, int32_t channels);
+int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream);
+/* HumanML3D features (n_seq, n_frames, channels >= 4 + 3 (joints_num - 1)) -> joints_out (n_seq, n_frames, joints_num, 3) (plot_script.py:15-52): root yaw
+ * = exclusive prefix sum of channel 0, quaternion (cos a, 0, sin a, 0) as the reference has it, root xz = inclusive prefix sum of the previous frame's
+ * velocity turned by its inverse, y = channel 3; the joints turned the same way and moved by the root's xz.  root_quat (n_seq, n_frames, 4) or NULL: the
+ * root quaternions (recover_root_rot_pos's first result; joint 0 of joints_out is its second).  One workgroup scan per sequence. */
+int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
+                         void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

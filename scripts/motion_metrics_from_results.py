@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""L1 diversity and beat consistency of a results directory as the reference's `test()` writes it (diffusion_rvqvae_trainer.py:702-709:
+`res_<id>.npz` with `poses` (n, 165) SMPL-X axis-angle, `trans`, `betas`), the way `test()` computes them (:626-638, 668, 677-684, 722-728).
+
+    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR]
+
+Per take: rest joints and the hands' mean pose from the model file and the take's betas (joints.smplx_rest_joints, host), the 55 skeleton joints by
+forward kinematics on the device with zero transl as `test()` passes it (joints.smplx_joints; the hand mean pose is added to the hand joints'
+axis-angle vectors, as smplx does for the reference's model, built without flat_hand_mean), L1div.run on them, and - with --onsets - the beat
+consistency of the slice [mask, n - mask) against the take's audio onsets.
+--mean-vel   the reference's `avg_vel` (55,): data_path + weights/mean_vel_<pose_rep>.npy
+--onsets     a directory with `<id>.npy`: onset times in seconds (what alignment.load_audio returns for the take's audio cut to the slice,
+             librosa.onset.onset_detect); a take without its file, or with no onsets, is left out of `bc` (named on stderr)
+--flat-hand-mean   for results made with a model built with flat_hand_mean=True: no hand mean pose is added
+--mask       frames dropped at either end (align_mask, default 60); takes of 2 mask frames or fewer are left out of `bc`
+Prints one JSON line: {"takes", "frames", "l1div"[, "bc", "bc_takes", "bc_frames"]}; bc = sum(align x (n - 2 mask)) / bc_frames over the bc_takes takes
+that have onsets, bc_frames = their frames - 2 bc_takes mask: the reference's weighting (:684, :722) when bc_takes == takes, and a partial figure,
+recognisable by bc_takes < takes, otherwise.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from syntalker_amd import joints, metrics  # noqa: E402
+
+
+def read_ids(results_dir: str):
+    return sorted(n[len("res_"):-len(".npz")] for n in os.listdir(results_dir) if n.startswith("res_") and n.endswith(".npz"))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("results_dir")
+    ap.add_argument("--smplx-model", required=True)
+    ap.add_argument("--mean-vel", required=True)
+    ap.add_argument("--onsets")
+    ap.add_argument("--flat-hand-mean", action="store_true")
+    ap.add_argument("--mask", type=int, default=60)
+    ap.add_argument("--sigma", type=float, default=0.3)
+    ap.add_argument("--order", type=int, default=7)
+    a = ap.parse_args(argv)
+    ids = read_ids(a.results_dir)
+    if not ids:
+        raise SystemExit(f"motion_metrics_from_results: no res_<id>.npz in {a.results_dir}")
+    model = dict(np.load(a.smplx_model, allow_pickle=True))
+    mmae = np.load(a.mean_vel)
+    dev = torch.device("cuda")
+    l1, align, bc_frames, bc_takes, frames = metrics.L1div(), 0.0, 0, 0, 0
+    for i in ids:
+        res = np.load(os.path.join(a.results_dir, f"res_{i}.npz"), allow_pickle=True)
+        pose = torch.from_numpy(np.asarray(res["poses"], dtype=np.float32)).to(dev)
+        n = pose.shape[0]
+        skel = joints.smplx_rest_joints(model, np.asarray(res["betas"], dtype=np.float64).reshape(-1), flat_hand_mean=a.flat_hand_mean)
+        joints_rec = joints.smplx_joints(skel, pose.reshape(n, -1))
+        l1.run(joints_rec)
+        frames += n
+        if a.onsets is None:
+            continue
+        path = os.path.join(a.onsets, f"{i}.npy")
+        onsets = np.load(path).reshape(-1) if os.path.exists(path) else np.zeros(0)
+        if onsets.size == 0 or n <= 2 * a.mask:
+            print(f"motion_metrics_from_results: {i} has no onsets (or is not longer than twice the mask), left out of bc", file=sys.stderr)
+            continue
+        align += metrics.beat_consistency(joints_rec, onsets, mmae, align_mask=a.mask, sigma=a.sigma, order=a.order) * (n - 2 * a.mask)
+        bc_frames += n - 2 * a.mask
+        bc_takes += 1
+    out = {"takes": len(ids), "frames": int(frames), "l1div": l1.avg()}
+    if a.onsets is not None:
+        out.update({"bc": align / bc_frames if bc_frames else None, "bc_takes": bc_takes, "bc_frames": int(bc_frames)})
+    print(json.dumps(out), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1773,6 +1773,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_plms.inc"
 #include "syn_bpd.inc"
 #include "syn_guide.inc"
+#include "syn_joints.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2291,6 +2292,37 @@ int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_c
 int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
                      uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream) {
     return guide::update(mode, a, pred_x0, grad, noise, draw, seed, first_clip, coef, n_rows, t_idx, n_clips, out, stream);
+}
+
+// Motion metrics (syn_joints.inc)
+int syn_fk_joints(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* rot, int32_t rot6d, const float* transl,
+                  const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, const float* pose_mean, float* joints_out, void* stream) {
+    return joints::fk(parents, n_joints, rest_joints, n_takes, rot, rot6d, transl, take_of_frame, frames_per_take, n_frames, pose_mean, joints_out, stream);
+}
+
+int syn_joint_speed(const float* joints_in, int32_t n_takes, int32_t n_frames, int32_t n_joints, float fps, const float* mmae, float* speed, void* stream) {
+    return joints::speed(joints_in, n_takes, n_frames, n_joints, fps, mmae, speed, stream);
+}
+
+int syn_motion_beats(const float* vel, int32_t n_takes, int32_t n_frames, int32_t n_joints, int32_t t_start, int32_t t_end, int32_t order, float threshold,
+                     uint8_t* mask, void* stream) {
+    return joints::beats(vel, n_takes, n_frames, n_joints, t_start, t_end, order, threshold, mask, stream);
+}
+
+int syn_beat_align(const uint8_t* mask, int32_t n_takes, int32_t n_slice, int32_t n_joints, const int32_t* upper_body, int32_t n_upper, const double* onsets,
+                   const int32_t* onset_offsets, double pose_fps, float sigma, float* per_joint, float* bc, void* stream) {
+    return joints::align(mask, n_takes, n_slice, n_joints, upper_body, n_upper, onsets, onset_offsets, pose_fps, sigma, per_joint, bc, stream);
+}
+
+int64_t syn_l1div_workspace_bytes(int32_t n_takes, int64_t n, int32_t channels) { return joints::l1div_workspace(n_takes, n, channels); }
+
+int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
+    return joints::l1div(x, n_takes, n, channels, workspace, blocks, out, stream);
+}
+
+int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
+                         void* stream) {
+    return joints::recover_from_ric(data, n_seq, n_frames, channels, joints_num, joints_out, root_quat, stream);
 }
 
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {

@@ -39,10 +39,16 @@ _MAP_EVAL = {"models.motion_representation": "syntalker_amd.dropin.models.motion
 _MAP_T2M = {"utils.t2m_eval_tools": "syntalker_amd.dropin.utils.t2m_eval_tools"}
 
 
-def install(rvqvae: bool = False, evaluator: bool = False, t2m: bool = False):
+# opt-in, same package: `utils.metric` - L1div and alignment (beat consistency) on the device; the reference's SRGR, which nothing calls, is not in it
+_MAP_METRIC = {"utils.metric": "syntalker_amd.dropin.utils.metric"}
+
+
+def install(rvqvae: bool = False, evaluator: bool = False, t2m: bool = False, metric: bool = False):
     """Alias the hot-path modules under the reference's module names (rvqvae=True: also `models.vq.model.RVQVAE`; evaluator=True: also
-    `models.motion_representation.VAESKConv`, the FGD evaluator; t2m=True: also `utils.t2m_eval_tools`, the h3d text-motion evaluator)."""
-    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {}), **(_MAP_EVAL if evaluator else {}), **(_MAP_T2M if t2m else {})}.items():
+    `models.motion_representation.VAESKConv`, the FGD evaluator; t2m=True: also `utils.t2m_eval_tools`, the h3d text-motion evaluator;
+    metric=True: also `utils.metric`, L1div and the beat-consistency `alignment`)."""
+    for ref_name, ours in {**_MAP, **(_MAP_RVQ if rvqvae else {}), **(_MAP_EVAL if evaluator else {}), **(_MAP_T2M if t2m else {}),
+                           **(_MAP_METRIC if metric else {})}.items():
         mod = importlib.import_module(ours)
         sys.modules[ref_name] = mod
         parent, _, leaf = ref_name.rpartition(".")

@@ -6,6 +6,9 @@ encoder (weights/AESKConv_240_100.bin - not distributed with the repository).  T
 (numpy / scipy like the reference's), and `fgd`, which runs it over that encoder's embeddings (evaluator.VAESKConv on the HIP
 kernels) the way the reference's `test()` collects them.  `latent_embedding` - time-averaged sampler latents in a fixed seeded
 projection - is the stand-in where no evaluator is at hand.
+
+Further down: the h3d text-motion metrics, and the beatx evaluation's other two numbers - `L1div` and `alignment` (beat consistency) of
+utils/metric.py on the kernels of csrc/syn_joints.inc, over the skeleton joints of `syntalker_amd.joints`.
 """
 from __future__ import annotations
 
@@ -258,3 +261,181 @@ def evaluate_multimodality(eval_wrapper, mm_motion_loaders, file, mm_num_times):
         _say(file, f"---> [{name}] Multimodality: {multimodality:.4f}")
         eval_dict[name] = multimodality
     return eval_dict
+
+
+# ---- the beatx evaluation's other two numbers: L1 diversity and beat consistency (utils/metric.py:12-27, 54-241) -----------------------
+# The reference's classes with their signatures and return types, numpy in and out as `test()` uses them (diffusion_rvqvae_trainer.py:677-684),
+# on the kernels of csrc/syn_joints.inc; device tensors are taken as they are.  `SRGR` has no caller in the reference and is not here.
+
+UPPER_BODY = (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)
+
+
+def _device_f32(x, what):
+    """numpy array or tensor -> contiguous fp32 tensor on the GPU (a CPU TENSOR is refused like everywhere else; arrays are the reference's
+    host interface and are copied to the current device)."""
+    import torch
+    from . import engine
+    if torch.is_tensor(x):
+        engine._require_cuda(x, what)
+        return x.detach().float().contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).cuda()
+
+
+def l1_sum(x, blocks: int = 0):
+    """sum |x - mean over rows| of an (n, C) array -> float, or of each of T equally long takes (T, n, C) -> (T,) float64 numpy, in one call
+    (`syn_l1div`): fp64 sums in a fixed order, the input left as it is.  `blocks`: the grid of the two passes (0: the library's choice) - the
+    result does not depend on it."""
+    import torch
+    from . import _lib
+    x = _device_f32(x, "L1div input")
+    if x.dim() not in (2, 3) or x.numel() == 0:
+        raise ValueError(f"l1_sum: a non-empty (n, C) or (T, n, C) array, got {tuple(x.shape)}")
+    t, (n, c) = (x.shape[0] if x.dim() == 3 else 1), x.shape[-2:]
+    lib = _lib.load()
+    ws = torch.empty(lib.syn_l1div_workspace_bytes(t, n, c) // 8, dtype=torch.float64, device=x.device)
+    out = torch.empty(t, dtype=torch.float64, device=x.device)
+    _lib.check(lib.syn_l1div(x.data_ptr(), t, n, c, ws.data_ptr(), int(blocks), out.data_ptr(), _lib.current_stream(x.device)), "syn_l1div")
+    return out.cpu().numpy() if x.dim() == 3 else float(out.item())
+
+
+class L1div(object):
+    """utils/metric.py:12-27.  `run` does NOT overwrite its argument (the reference's does: it leaves the deviations in `results`)."""
+
+    def __init__(self):
+        self.counter = 0
+        self.sum = 0
+
+    def run(self, results):
+        self.counter += results.shape[0]
+        self.sum += l1_sum(results)
+
+    def avg(self):
+        return self.sum / self.counter
+
+    def reset(self):
+        self.counter = 0
+        self.sum = 0
+
+
+def motion_beat_mask(vel, t_start: int, t_end: int, order: int, threshold: float = 0.3):
+    """vel (n, J) or (T, n, J) device speeds -> uint8 mask (n_slice, J) / (T, n_slice, J) of `syn_motion_beats` over the slice vel[t_start:t_end]
+    (Python slice semantics).  Entry (j, i) says slice index j is a beat of joint i - with the reference's threshold test on vel[j, i], not
+    vel[j + t_start, i] (utils/metric.py:113-123)."""
+    import torch
+    from . import _lib, engine
+    engine._require_cuda(vel, "speeds")
+    v = vel.detach().float().contiguous()
+    batched = v.dim() == 3
+    if v.dim() not in (2, 3):
+        raise ValueError(f"motion_beat_mask: speeds are (n, J) or (T, n, J), got {tuple(vel.shape)}")
+    v3 = v if batched else v[None]
+    t, n, j = v3.shape
+    s, e, _ = slice(t_start, t_end).indices(n)
+    e = max(e, s)
+    mask = torch.zeros(t, e - s, j, dtype=torch.uint8, device=v.device)
+    if mask.numel():
+        _lib.check(_lib.load().syn_motion_beats(v3.data_ptr(), t, n, j, s, e, int(order), float(threshold), mask.data_ptr(), _lib.current_stream(v.device)),
+                   "syn_motion_beats")
+    return mask if batched else mask[0]
+
+
+def beat_align(mask, onset_times, upper_body=UPPER_BODY, pose_fps: float = 30.0, sigma: float = 0.3):
+    """mask (n_slice, J) / (T, n_slice, J) uint8 on the device; onset_times: seconds, one array (or one per take) -> (per_joint (U,) / (T, U), bc
+    float / (T,)) as numpy (`syn_beat_align`).  No onsets in a take: ValueError (the reference divides by zero there)."""
+    import torch
+    from . import _lib, engine
+    engine._require_cuda(mask, "beat mask")
+    batched = mask.dim() == 3
+    m = (mask if batched else mask[None]).to(torch.uint8).contiguous()
+    t, n_slice, j = m.shape
+    per_take = [np.asarray(o, dtype=np.float64).reshape(-1) for o in (onset_times if batched else [onset_times])]
+    if len(per_take) != t:
+        raise ValueError(f"beat_align: {t} takes, {len(per_take)} onset lists")
+    if any(o.size == 0 for o in per_take):
+        raise ValueError("beat_align: a take without audio onsets has no beat consistency (the mean over its onsets is 0 / 0)")
+    ub = np.asarray(list(upper_body), dtype=np.int32)
+    if ub.size == 0 or ub.min() < 0 or ub.max() >= j:
+        raise ValueError(f"beat_align: upper_body must name joints of [0, {j})")
+    dev = m.device
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum([o.size for o in per_take])]).astype(np.int32)).to(dev)
+    ons = torch.from_numpy(np.concatenate(per_take)).to(dev)
+    ubt = torch.from_numpy(ub).to(dev)
+    per_joint = torch.empty(t, ub.size, dtype=torch.float32, device=dev)
+    bc = torch.empty(t, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().syn_beat_align(m.data_ptr(), t, n_slice, j, ubt.data_ptr(), int(ub.size), ons.data_ptr(), offs.data_ptr(), float(pose_fps),
+                                          float(sigma), per_joint.data_ptr(), bc.data_ptr(), _lib.current_stream(dev)), "syn_beat_align")
+    pj, b = per_joint.cpu().numpy(), bc.cpu().numpy()
+    return (pj, b) if batched else (pj[0], float(b[0]))
+
+
+class alignment(object):
+    """utils/metric.py:54-241 with the reference's signatures.  `load_pose` and `calculate_align` run on the device; `load_audio` is librosa's
+    onset detector and nothing else, so it stays librosa's (imported when called)."""
+
+    def __init__(self, sigma, order, mmae=None, upper_body=[3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21]):
+        self.sigma = sigma
+        self.order = order
+        self.upper_body = upper_body
+        self.pose_data = []
+        self.mmae = mmae
+        self.threshold = 0.3
+
+    def load_audio(self, wave, t_start=None, t_end=None, without_file=False, sr_audio=16000):
+        try:
+            import librosa
+        except ImportError as e:
+            raise ImportError("alignment.load_audio needs librosa (librosa.onset.onset_detect finds the audio onsets); it is not installed. "
+                              "Compute the onset times elsewhere and pass them to calculate_align / beat_consistency.") from e
+        y = wave if without_file else librosa.load(wave)[0]
+        short_y = y if t_start is None else y[t_start:t_end]
+        return librosa.onset.onset_detect(y=short_y, sr=sr_audio, hop_length=512, units="time")
+
+    def load_pose(self, pose, t_start, t_end, pose_fps, without_file=False):
+        """pose (n, J * 3) joints -> one array of beat indices (slice indices) per joint."""
+        if not without_file:
+            raise NotImplementedError("alignment.load_pose reads joints from memory (without_file=True, as test() calls it); the BVH text reader is not ported")
+        from . import joints as jt
+        mask = motion_beat_mask(jt.joint_speed(_device_f32(pose, "pose"), pose_fps, self.mmae), t_start, t_end, self.order, self.threshold).cpu().numpy()
+        return [np.array(np.nonzero(mask[:, i])[0].tolist()) for i in range(mask.shape[1])]       # (an empty list gives the reference's float64 empty array)
+
+    @staticmethod
+    def motion_frames2time(vel, offset, pose_fps):
+        return vel / pose_fps + offset
+
+    @staticmethod
+    def GAHR(a, b, sigma):
+        """Mean over b of exp(-min_a |a - b|^2 / 2 sigma^2) (0 for an empty a): one (take, joint) of `syn_beat_align`, on the host in fp64 for
+        callers that hold times rather than a beat mask."""
+        a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
+        if b.size == 0:
+            raise ValueError("GAHR: no audio onsets (the mean over them is 0 / 0)")
+        if a.size == 0:
+            return 0.0
+        d = np.abs(a[None, :] - b[:, None]).min(1)
+        return float(np.exp(-(d ** 2) / (2 * sigma ** 2)).sum() / b.size)
+
+    def calculate_align(self, onset_bt_rms, beat_vel, pose_fps=30):
+        """onset times (seconds) and `load_pose`'s list -> the mean over the upper-body joints of GAHR(beat times, onsets)."""
+        import torch
+        onsets = np.asarray(onset_bt_rms, dtype=np.float64).reshape(-1)
+        if onsets.size == 0:
+            raise ValueError("calculate_align: no audio onsets (the reference divides by zero here)")
+        n_slice = 1 + max([int(np.max(b)) for b in beat_vel if len(b)], default=0)
+        mask = np.zeros((n_slice, len(beat_vel)), dtype=np.uint8)
+        for i, b in enumerate(beat_vel):
+            if len(b):
+                mask[np.asarray(b, dtype=np.int64), i] = 1
+        return beat_align(torch.from_numpy(mask).cuda(), onsets, self.upper_body, pose_fps, self.sigma)[1]
+
+
+def beat_consistency(joints, onset_times, mmae, align_mask: int = 60, sigma: float = 0.3, order: int = 7, upper_body=UPPER_BODY, pose_fps: float = 30.0,
+                     threshold: float = 0.3):
+    """BC of one take, or of T equally long takes, in one pass on the device: joints (n, J * 3) | (n, J, 3) | (T, n, J, 3) -> speeds / mmae ->
+    beats of the slice [align_mask, n - align_mask) -> alignment with the onsets (seconds; one array, or one per take).  What `test()` computes
+    per take at diffusion_rvqvae_trainer.py:683-684 (there: sigma 0.3, order 7, mask 60).  Returns a float, or (T,) numpy."""
+    from . import joints as jt
+    x = _device_f32(joints, "joints")
+    vel = jt.joint_speed(x, pose_fps, mmae)
+    n = vel.shape[-2]
+    mask = motion_beat_mask(vel, align_mask, n - align_mask, order, threshold)
+    return beat_align(mask, onset_times, upper_body, pose_fps, sigma)[1]
