@@ -276,6 +276,44 @@ int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void
 int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
                          void* stream);
 
+/* The SMPL-X mesh: linear blend skinning of the model's vertices, what smplx(...)["vertices"] gives test() (:640-675) and the renderers (additive,
+ * SYN_ABI_VERSION stays 9; csrc/syn_mesh.inc).  fp32 device tensors unless noted; deterministic, no floating-point atomics; every call
+ * enqueues on `stream`, allocates nothing and is graph-capturable.  J = n_joints, P = 9 (J - 1) pose-corrective directions, E = n_expr expression
+ * directions, Kc = P + E <= 1024, Kcp = Kc rounded up to 16, Vp = n_verts rounded up to 64.
+ *
+ * syn_mesh_pack_dirs: posedirs (n_verts, 3, n_pose) and exprdirs (n_verts, 3, n_expr) (NULL with n_expr == 0), as the model file lays them out, ->
+ * out [Vp / 16][Kcp / 16][3][64][4] floats (Vp * 3 * Kcp): the B fragments of v_mfma_f32_16x16x4_f32, lane l of tile t, group g, plane p, element u =
+ * direction k = 16 g + 4 (l >> 4) + u (pose correctives first, then expressions) of coordinate p of vertex 16 t + (l & 15); zero for k >= Kc and for
+ * vertices >= n_verts. */
+int syn_mesh_pack_dirs(const float* posedirs, const float* exprdirs, int32_t n_verts, int32_t n_pose, int32_t n_expr, float* out, void* stream);
+/* The joint transforms of n_frames poses: syn_fk_joints' tree walk (2 <= n_joints <= 64; parents, rest_joints (n_takes, n_joints, 3), pose_mean,
+ * take_of_frame / frames_per_take as there: a take outside [0, n_takes) gives NaN transforms and joints, nothing read for it).  pose (n_frames, J, 3)
+ * axis-angle.  With n_expr > 0 frame n's rest joints are its take's + joint_dirs (J, 3, n_expr) . expression (n_frames, n_expr) - SMPL-X regresses
+ * the joints from the shaped vertices, expression term included; n_expr == 0: no expression (zero), whatever the mesh's directions hold.  kc: the
+ * contraction length of the syn_mesh_vertices call that follows, 9 (J - 1) + n_expr <= kc <= 1024.  Outputs:
+ *   feat (n_frames, Kcp)          R_j - I of joints 1 .. J - 1 row-major (the pose feature), then the expression, then zeros up to Kcp = kc rounded up
+ *                                 to 16: syn_mesh_vertices' A rows
+ *   xforms (n_frames, J, 3, 4)    the rows of A_j = [G_j^R | G_j^t - G_j^R J_rest,j], G_j = G_parent . [R_j | J_rest,j - J_rest,parent]
+ *   joints_out (n_frames, J, 3)   G_j^t + transl (n_frames, 3) (or NULL).  With n_expr == 0 they are written by syn_fk_joints' own kernel: its bits, for the
+ *                                 same arguments */
+int syn_fk_transforms(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* pose, const float* pose_mean,
+                      const float* joint_dirs, const float* expression, int32_t n_expr, int32_t kc, const float* transl, const int32_t* take_of_frame,
+                      int32_t frames_per_take, int64_t n_frames, float* feat, float* xforms, float* joints_out, void* stream);
+/* vertices_out (n_frames, n_verts, 3) = sum_j w_vj (A_j^R v_posed + A_j^t) + transl, v_posed = v_shaped[take] + dirs . feat, in one kernel: v_posed
+ * stays in the MFMA accumulators.  dirs_packed: syn_mesh_pack_dirs' output for the same n_verts and kc; feat, xforms: syn_fk_transforms' (all three
+ * 16-byte aligned); v_shaped (n_takes, n_verts, 3); the skin weights as fixed-width lists, skin_index / skin_weight (n_verts, width), 1 <= width <=
+ * n_joints, entries with weight 0 skipped (the padding of a shorter list), indices clamped to [0, J).  A take outside [0, n_takes): NaN vertices.  Every
+ * element is summed in an order fixed by kc and the vertex's list: a frame's vertices are bitwise the same whichever frames share the call. */
+int syn_mesh_vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, const float* feat, const float* xforms, int32_t n_joints,
+                      const float* v_shaped, int32_t n_takes, const int32_t* skin_index, const float* skin_weight, int32_t width, const float* transl,
+                      const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* vertices_out, void* stream);
+/* test()'s face numbers (:672-673) of rec, tar (n, channels): out[0] = mean (rec - tar)^2; out[1] = mean |(rec[1:] - tar[:-1]) - (tar[1:] - tar[:-1])|
+ * as the reference writes it (fp32 differences), NaN for n == 1.  fp64 sums in an order fixed by (n, channels) alone: bitwise the same on every run and
+ * for every `blocks` (the grid; 0 = the library's choice).  workspace: syn_vertex_losses_workspace_bytes(n, channels) bytes (-1 for counts below 1),
+ * 8-byte aligned like out. */
+int64_t syn_vertex_losses_workspace_bytes(int64_t n, int32_t channels);
+int syn_vertex_losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

@@ -2,7 +2,7 @@
 """L1 diversity and beat consistency of a results directory as the reference's `test()` writes it (diffusion_rvqvae_trainer.py:702-709:
 `res_<id>.npz` with `poses` (n, 165) SMPL-X axis-angle, `trans`, `betas`), the way `test()` computes them (:626-638, 668, 677-684, 722-728).
 
-    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR]
+    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR] [--face]
 
 Per take: rest joints and the hands' mean pose from the model file and the take's betas (joints.smplx_rest_joints, host), the 55 skeleton joints by
 forward kinematics on the device with zero transl as `test()` passes it (joints.smplx_joints; the hand mean pose is added to the hand joints'
@@ -12,8 +12,10 @@ consistency of the slice [mask, n - mask) against the take's audio onsets.
 --onsets     a directory with `<id>.npy`: onset times in seconds (what alignment.load_audio returns for the take's audio cut to the slice,
              librosa.onset.onset_detect); a take without its file, or with no onsets, is left out of `bc` (named on stderr)
 --flat-hand-mean   for results made with a model built with flat_hand_mean=True: no hand mean pose is added
+--face       also test()'s `l2 loss` and `lvel loss` (:640-675, :713-714): the face meshes of `res_<id>.npz` against `gt_<id>.npz` (jaw pose and
+             `expressions` of each, everything else zero; metrics.face_losses), accumulated as test() does: sum(value x n) / frames
 --mask       frames dropped at either end (align_mask, default 60); takes of 2 mask frames or fewer are left out of `bc`
-Prints one JSON line: {"takes", "frames", "l1div"[, "bc", "bc_takes", "bc_frames"]}; bc = sum(align x (n - 2 mask)) / bc_frames over the bc_takes takes
+Prints one JSON line: {"takes", "frames", "l1div"[, "bc", "bc_takes", "bc_frames"][, "l2", "lvel"]}; bc = sum(align x (n - 2 mask)) / bc_frames over the bc_takes takes
 that have onsets, bc_frames = their frames - 2 bc_takes mask: the reference's weighting (:684, :722) when bc_takes == takes, and a partial figure,
 recognisable by bc_takes < takes, otherwise.
 """
@@ -26,7 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from syntalker_amd import joints, metrics  # noqa: E402
+from syntalker_amd import joints, mesh, metrics  # noqa: E402
 
 
 def read_ids(results_dir: str):
@@ -40,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--mean-vel", required=True)
     ap.add_argument("--onsets")
     ap.add_argument("--flat-hand-mean", action="store_true")
+    ap.add_argument("--face", action="store_true")
     ap.add_argument("--mask", type=int, default=60)
     ap.add_argument("--sigma", type=float, default=0.3)
     ap.add_argument("--order", type=int, default=7)
@@ -51,6 +54,7 @@ def main(argv=None):
     mmae = np.load(a.mean_vel)
     dev = torch.device("cuda")
     l1, align, bc_frames, bc_takes, frames = metrics.L1div(), 0.0, 0, 0, 0
+    l2_all, lvel_all = 0.0, 0.0
     for i in ids:
         res = np.load(os.path.join(a.results_dir, f"res_{i}.npz"), allow_pickle=True)
         pose = torch.from_numpy(np.asarray(res["poses"], dtype=np.float32)).to(dev)
@@ -59,6 +63,14 @@ def main(argv=None):
         joints_rec = joints.smplx_joints(skel, pose.reshape(n, -1))
         l1.run(joints_rec)
         frames += n
+        if a.face:
+            gt = np.load(os.path.join(a.results_dir, f"gt_{i}.npz"), allow_pickle=True)
+            face = mesh.smplx_mesh(model, np.asarray(res["betas"], dtype=np.float64).reshape(-1), flat_hand_mean=a.flat_hand_mean)
+            to_dev = lambda x: torch.from_numpy(np.asarray(x, dtype=np.float32)).to(dev)
+            l2, lvel = metrics.face_losses(face, pose.reshape(n, -1), to_dev(gt["poses"]).reshape(n, -1), to_dev(res["expressions"]).reshape(n, -1),
+                                           to_dev(gt["expressions"]).reshape(n, -1))
+            l2_all += l2 * n
+            lvel_all += lvel * n
         if a.onsets is None:
             continue
         path = os.path.join(a.onsets, f"{i}.npy")
@@ -72,6 +84,8 @@ def main(argv=None):
     out = {"takes": len(ids), "frames": int(frames), "l1div": l1.avg()}
     if a.onsets is not None:
         out.update({"bc": align / bc_frames if bc_frames else None, "bc_takes": bc_takes, "bc_frames": int(bc_frames)})
+    if a.face:
+        out.update({"l2": l2_all / frames, "lvel": lvel_all / frames})
     print(json.dumps(out), flush=True)
     return out
 

@@ -32,7 +32,8 @@ EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_ste
            "syn_vq_train_codebook_prep", "syn_vq_train_tile", "syn_vq_train_quantize", "syn_vq_train_codebook_update",
            "syn_vq_train_loss_parts", "syn_vq_train_loss", "syn_vq_train_scalars", "syn_plms_update", "syn_bpd_terms",
            "syn_guide_in_fwd", "syn_guide_in_bwd", "syn_guide_update",
-           "syn_fk_joints", "syn_joint_speed", "syn_motion_beats", "syn_beat_align", "syn_l1div_workspace_bytes", "syn_l1div", "syn_recover_from_ric")
+           "syn_fk_joints", "syn_joint_speed", "syn_motion_beats", "syn_beat_align", "syn_l1div_workspace_bytes", "syn_l1div", "syn_recover_from_ric",
+           "syn_mesh_pack_dirs", "syn_fk_transforms", "syn_mesh_vertices", "syn_vertex_losses_workspace_bytes", "syn_vertex_losses")
 
 # the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
 DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
@@ -369,16 +370,22 @@ def load():
     lib.syn_l1div_workspace_bytes.argtypes = [i32, i64, i32]
     lib.syn_l1div.argtypes = [vp, i32, i64, i32, vp, i32, vp, vp]
     lib.syn_recover_from_ric.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.syn_mesh_pack_dirs.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    lib.syn_fk_transforms.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, vp, vp]
+    lib.syn_mesh_vertices.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, i64, vp, vp]
+    lib.syn_vertex_losses_workspace_bytes.argtypes = [i64, i32]
+    lib.syn_vertex_losses.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes",
-                        "syn_t2m_workspace_bytes", "syn_l1div_workspace_bytes"):
+                        "syn_t2m_workspace_bytes", "syn_l1div_workspace_bytes", "syn_vertex_losses_workspace_bytes"):
             fn.restype = C.c_int
     lib.syn_wav_workspace_bytes.restype = C.c_int64
     lib.syn_conv1d_pack_bytes.restype = C.c_int64
     lib.syn_vq_workspace_bytes.restype = C.c_int64
     lib.syn_t2m_workspace_bytes.restype = C.c_int64
     lib.syn_l1div_workspace_bytes.restype = C.c_int64
+    lib.syn_vertex_losses_workspace_bytes.restype = C.c_int64
     _lib = lib
     return lib
 

@@ -59,10 +59,28 @@ __device__ __forceinline__ void axis_angle_matrix(float x, float y, float z, flo
 // per-thread ancestor stack, nothing indexed dynamically in registers.  pose_mean [J][3] (or NULL) is added to the axis-angle vectors before
 // Rodrigues: SMPL-X's `full_pose += pose_mean`, the hands' mean pose of a model built with flat_hand_mean = False.  A parent that is not an earlier joint is treated as a root, so a malformed tree cannot send a shuffle
 // anywhere but to an earlier lane; a take index outside [0, n_takes) gives NaN joints.
+//
+// The mesh (syn_mesh.inc, syn_fk_transforms) instantiates this kernel with MESH = true.  That instance also writes, per frame, the A row of the
+// corrective product m.feat (N, Kcp) = [R_j - I of joints 1 .. J - 1 | expression | 0 ..] and m.xf (N, J, 3, 4), the rows of the skinning transform
+// A_j = [G_j^R | G_j^t - G_j^R rest_j]; the rest joints of frame n are the take's plus m.joint_dirs (J, 3, E) . m.expr[n] where m.expr is set;
+// transl is not folded into the root but added to the joints written (`out` may be NULL); axis-angle input only.  MESH = false is syn_fk_joints'
+// kernel, its code as it was: every `if constexpr (MESH)` below drops out of it.  The two instances are two compilations - hipcc contracts and
+// vectorises them differently, and their joints differ in the last bit - so what the mesh instance adds is written out in fmaf / fadd / fsub (the two
+// frame slots of a wave must round alike), and where the joints must be syn_fk_joints' bit for bit (no expression) syn_fk_transforms has the
+// MESH = false instance write them.
+struct FkMesh {
+    const float* joint_dirs; const float* expr;
+    float* feat; float* xf;
+    int E, Kcp;
+};
+
+template <bool MESH>
 __global__ __launch_bounds__(kFkThreads) void k_fk(const int* __restrict__ parents, int J, const float* __restrict__ rest, int n_takes,
                                                    const float* __restrict__ rot, int six, const float* __restrict__ transl,
                                                    const int* __restrict__ take_of_frame, int frames_per_take, long N, float* __restrict__ out,
-                                                   const float* __restrict__ pose_mean) {
+                                                   const float* __restrict__ pose_mean, const FkMesh m) {
+    [[maybe_unused]] const int P = 9 * (J - 1);
+    [[maybe_unused]] float rj[kFkWaveFrames][3];                 // MESH: the frame's rest joint of this lane
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool live = lane < J;
     int par = live ? parents[lane] : -1;
@@ -74,6 +92,13 @@ __global__ __launch_bounds__(kFkThreads) void k_fk(const int* __restrict__ paren
         const long n = nw + f;
 #pragma unroll
         for (int e = 0; e < 12; ++e) G[f][e] = 0.f;
+        if constexpr (MESH) {
+            rj[f][0] = rj[f][1] = rj[f][2] = 0.f;
+            if (n < N) {
+            float* __restrict__ frow = m.feat + n * m.Kcp;
+            for (int k = P + lane; k < m.Kcp; k += 64) frow[k] = (m.expr && k - P < m.E) ? m.expr[n * m.E + (k - P)] : 0.f;
+            }
+        }
         if (!live || n >= N) continue;
         float R[9];
         if (six) {
@@ -88,10 +113,16 @@ __global__ __launch_bounds__(kFkThreads) void k_fk(const int* __restrict__ paren
             }
             axis_angle_matrix(x, y, z, R);
         }
+        if constexpr (MESH) if (lane >= 1) {
+            float* __restrict__ frow = m.feat + n * m.Kcp + (lane - 1) * 9;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) frow[e] = (e == 0 || e == 4 || e == 8) ? __fsub_rn(R[e], 1.0f) : R[e];
+        }
         const int take = take_of_frame ? take_of_frame[n] : (int)(n / frames_per_take);
         float t[3];
         if (take < 0 || take >= n_takes) {
             t[0] = t[1] = t[2] = __builtin_nanf("");
+            if constexpr (MESH) rj[f][0] = rj[f][1] = rj[f][2] = __builtin_nanf("");
         } else {
             const float* r = rest + ((long)take * J + lane) * 3;
             if (par >= 0) {
@@ -100,13 +131,37 @@ __global__ __launch_bounds__(kFkThreads) void k_fk(const int* __restrict__ paren
                 for (int e = 0; e < 3; ++e) t[e] = r[e] - rp[e];
             } else {
 #pragma unroll
-                for (int e = 0; e < 3; ++e) t[e] = transl ? r[e] + transl[n * 3 + e] : r[e];
+                for (int e = 0; e < 3; ++e) t[e] = (transl && !MESH) ? r[e] + transl[n * 3 + e] : r[e];
+            }
+            if constexpr (MESH) {
+#pragma unroll
+                for (int e = 0; e < 3; ++e) rj[f][e] = r[e];
+                if (m.expr) {
+                    const float* x = m.expr + n * m.E;
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) {
+                        const float* d = m.joint_dirs + ((long)lane * 3 + e) * m.E;
+                        float s = 0.f;
+                        for (int k = 0; k < m.E; ++k) s = __fmaf_rn(d[k], x[k], s);
+                        rj[f][e] = __fadd_rn(rj[f][e], s);
+                    }
+                }
             }
         }
 #pragma unroll
         for (int e = 0; e < 9; ++e) G[f][e] = R[e];
 #pragma unroll
         for (int e = 0; e < 3; ++e) G[f][9 + e] = t[e];
+    }
+    if constexpr (MESH) if (m.expr) {                            // the offsets between the MOVED rest joints (all 64 lanes are here again)
+        const int src = par >= 0 ? par : lane;
+#pragma unroll
+        for (int f = 0; f < kFkWaveFrames; ++f)
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const float rp = __shfl(rj[f][e], src);
+                G[f][9 + e] = par >= 0 ? __fsub_rn(rj[f][e], rp) : rj[f][e];
+            }
     }
     int anc = par;
     while (__builtin_amdgcn_ballot_w64(anc >= 0)) {               // (all 64 lanes of every wave are here: shuffles read live registers)
@@ -136,7 +191,17 @@ __global__ __launch_bounds__(kFkThreads) void k_fk(const int* __restrict__ paren
         const long n = nw + f;
         if (!live || n >= N) continue;
         float* __restrict__ dst = out + (n * J + lane) * 3;
-        dst[0] = G[f][9]; dst[1] = G[f][10]; dst[2] = G[f][11];
+        if constexpr (!MESH) {
+            dst[0] = G[f][9]; dst[1] = G[f][10]; dst[2] = G[f][11];
+        } else {
+        float* __restrict__ a = m.xf + (n * J + lane) * 12;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            a[4 * r] = G[f][3 * r]; a[4 * r + 1] = G[f][3 * r + 1]; a[4 * r + 2] = G[f][3 * r + 2];
+            a[4 * r + 3] = __fsub_rn(G[f][9 + r], __fmaf_rn(G[f][3 * r + 2], rj[f][2], __fmaf_rn(G[f][3 * r + 1], rj[f][1], __fmul_rn(G[f][3 * r], rj[f][0]))));
+            if (out) dst[r] = transl ? __fadd_rn(G[f][9 + r], transl[n * 3 + r]) : G[f][9 + r];
+        }
+        }
     }
 }
 
@@ -374,8 +439,8 @@ static int fk(const int32_t* parents, int32_t n_joints, const float* rest, int32
     if (n_frames == 0) return 0;
     const int64_t blocks = (n_frames + kFkFrames - 1) / kFkFrames;
     if (blocks > 0x7fffffffLL) return fail_msg("syn_fk_joints: too many frames for one launch");
-    hipLaunchKernelGGL(k_fk, dim3((unsigned)blocks), dim3(kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest, (int)n_takes,
-                       rot, (int)(six != 0), transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, out, pose_mean);
+    hipLaunchKernelGGL(k_fk<false>, dim3((unsigned)blocks), dim3(kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest, (int)n_takes,
+                       rot, (int)(six != 0), transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, out, pose_mean, FkMesh{});
     return launched("k_fk launch");
 }
 

@@ -1774,6 +1774,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_bpd.inc"
 #include "syn_guide.inc"
 #include "syn_joints.inc"
+#include "syn_mesh.inc"
 
 // ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
 struct WavPlan {
@@ -2323,6 +2324,31 @@ int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void
 int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
                          void* stream) {
     return joints::recover_from_ric(data, n_seq, n_frames, channels, joints_num, joints_out, root_quat, stream);
+}
+
+// SMPL-X mesh (syn_mesh.inc)
+int syn_mesh_pack_dirs(const float* posedirs, const float* exprdirs, int32_t n_verts, int32_t n_pose, int32_t n_expr, float* out, void* stream) {
+    return mesh::pack_dirs(posedirs, exprdirs, n_verts, n_pose, n_expr, out, stream);
+}
+
+int syn_fk_transforms(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* pose, const float* pose_mean,
+                      const float* joint_dirs, const float* expression, int32_t n_expr, int32_t kc, const float* transl, const int32_t* take_of_frame,
+                      int32_t frames_per_take, int64_t n_frames, float* feat, float* xforms, float* joints_out, void* stream) {
+    return mesh::fk_transforms(parents, n_joints, rest_joints, n_takes, pose, pose_mean, joint_dirs, expression, n_expr, kc, transl, take_of_frame,
+                               frames_per_take, n_frames, feat, xforms, joints_out, stream);
+}
+
+int syn_mesh_vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, const float* feat, const float* xforms, int32_t n_joints,
+                      const float* v_shaped, int32_t n_takes, const int32_t* skin_index, const float* skin_weight, int32_t width, const float* transl,
+                      const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* vertices_out, void* stream) {
+    return mesh::vertices(dirs_packed, n_verts, kc, feat, xforms, n_joints, v_shaped, n_takes, skin_index, skin_weight, width, transl, take_of_frame,
+                          frames_per_take, n_frames, vertices_out, stream);
+}
+
+int64_t syn_vertex_losses_workspace_bytes(int64_t n, int32_t channels) { return mesh::losses_workspace(n, channels); }
+
+int syn_vertex_losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
+    return mesh::losses(rec, tar, n, channels, workspace, blocks, out, stream);
 }
 
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {

@@ -439,3 +439,48 @@ def beat_consistency(joints, onset_times, mmae, align_mask: int = 60, sigma: flo
     n = vel.shape[-2]
     mask = motion_beat_mask(vel, align_mask, n - align_mask, order, threshold)
     return beat_align(mask, onset_times, upper_body, pose_fps, sigma)[1]
+
+
+# ---- the face numbers of test(): `l2 loss` and `lvel loss` over the face meshes (diffusion_rvqvae_trainer.py:640-675) -----------------------------
+def vertex_losses(rec_vertices, tar_vertices, blocks: int = 0):
+    """(l2, lvel) of two equally shaped vertex arrays (n, V, 3) | (n, C) as Python floats (`syn_vertex_losses`): l2 = mean (rec - tar)^2
+    (nn.MSELoss, :673); lvel = mean |(rec[1:] - tar[:-1]) - (tar[1:] - tar[:-1])| (nn.L1Loss on the two differences AS WRITTEN at :672 - the
+    reference differences `rec` against the previous TARGET frame), fp32 differences, fp64 sums in a fixed order.  n = 1: lvel is NaN.  `blocks`: the
+    grid (0: the library's choice) - the result does not depend on it."""
+    import torch
+    from . import _lib
+    r, t = _device_f32(rec_vertices, "rec vertices"), _device_f32(tar_vertices, "tar vertices")
+    if r.shape != t.shape or r.dim() < 2 or r.numel() == 0:
+        raise ValueError(f"vertex_losses: two non-empty arrays of one shape (n, ...), got {tuple(r.shape)} and {tuple(t.shape)}")
+    n, c = r.shape[0], r.numel() // r.shape[0]
+    lib = _lib.load()
+    ws = torch.empty(lib.syn_vertex_losses_workspace_bytes(n, c) // 8, dtype=torch.float64, device=r.device)
+    out = torch.empty(2, dtype=torch.float64, device=r.device)
+    _lib.check(lib.syn_vertex_losses(r.data_ptr(), t.data_ptr(), n, c, ws.data_ptr(), int(blocks), out.data_ptr(), _lib.current_stream(r.device)),
+               "syn_vertex_losses")
+    l2, lvel = out.cpu().tolist()
+    return l2, lvel
+
+
+JAW = slice(66, 69)          # the jaw's axis-angle vector in test()'s (n, 165) pose
+
+
+def face_losses(model, rec_pose, tar_pose, rec_exps, tar_exps):
+    """diffusion_rvqvae_trainer.py:640-675 in one call: both face meshes with zero global, body, eye and hand pose and zero transl (the hands' mean
+    pose is still added: `smplx` adds `pose_mean` to a zero hand pose too), each with its OWN jaw pose (:644, :658) and expression, then
+    `vertex_losses`.  model: `mesh.smplx_mesh` of the take's betas; poses (n, 165) axis-angle or (n, 330) 6D; expressions (n, E).  Returns (l2, lvel),
+    to be weighted by n as test() does (:674-675)."""
+    import torch
+    from . import engine, mesh, poses
+
+    def face(pose, exps):
+        engine._require_cuda(pose, "pose")
+        p = pose.detach().float().reshape(-1, pose.shape[-1])
+        if p.shape[1] == 330:
+            p = poses.rotation_6d_to_axis_angle(p.reshape(-1, 55, 6)).reshape(-1, 165)
+        if p.shape[1] != 165:
+            raise ValueError(f"face_losses: poses are (n, 165) axis-angle or (n, 330) 6D, got {tuple(pose.shape)}")
+        jaw_only = torch.zeros_like(p)
+        jaw_only[:, JAW] = p[:, JAW]
+        return mesh.smplx_vertices(model, jaw_only, exps)
+    return vertex_losses(face(rec_pose, rec_exps), face(tar_pose, tar_exps))
