@@ -8,36 +8,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SYN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsyn_hip.so")   # env override: kernel A/B builds
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "syn_hip.h")      # the C ABI: the ctypes signatures below are read from it
 
 SYN_LAYERS = 8
 ABI_VERSION = 9             # include/syn_hip.h SYN_ABI_VERSION: a library built from other sources is refused at load time
-EXPORTS = ("syn_version", "syn_last_error", "syn_denoise_step", "syn_denoise_step_edit", "syn_denoise_steps", "syn_denoise_step_profile", "syn_pack_weight", "syn_pack_weight_t", "syn_to_token_major",
-           "syn_from_token_major", "syn_axpby_rows", "syn_randn", "syn_linear", "syn_linear_pair", "syn_linear_and_pack", "syn_linear_res", "syn_linear_gelu", "syn_opt_blocks", "syn_opt_sqnorm", "syn_opt_scalars", "syn_opt_adam", "syn_test_gemm", "syn_test_attention", "syn_test_handoff",
-           "syn_wav_encode", "syn_wav_workspace_bytes", "syn_wav_out_frames", "syn_linear_bwd_prep", "syn_embedding_wgrad", "syn_pack_weights", "syn_bn_chunks", "syn_bn_act_fwd", "syn_bn_act_bwd", "syn_bn_sums", "syn_bn_act_apply", "syn_bn_bwd_sums", "syn_bn_act_bwd_apply", "syn_conv1d_train_fwd", "syn_conv1d_train_fwd_tiles", "syn_conv1d_pack_split", "syn_conv1d_pack_split_many", "syn_conv1d_pack_bytes", "syn_conv1d_train_wgrad", "syn_conv1d_train_wgrad_pair", "syn_conv1d_wgrad_shares", "syn_conv1d_first_parts", "syn_conv1d_first_fwd", "syn_conv1d_first_wgrad", "syn_conv1d_first_wgrad_tail", "syn_conv1d_first_wgrad_bn_lin", "syn_cond_encode",
-           "syn_vq_conv1d", "syn_vq_quantize", "syn_vq_quantize_groups", "syn_vq_codes",
-           "syn_vq_workspace_bytes", "syn_vq_map2latent", "syn_vq_latent2origin", "syn_vq_forward_decoder",
-           "syn_step_advance", "syn_steps_advance", "syn_prefers_fragment_order", "syn_x_to_fragment", "syn_x_from_fragment", "syn_ln_fwd", "syn_ln_bwd", "syn_gelu_fwd", "syn_gelu_bwd", "syn_attn_fwd", "syn_attn_bwd",
-           "syn_axis_angle_to_rot6d", "syn_rot6d_to_axis_angle", "syn_rotary", "syn_linear_wgrad_rows", "syn_masked_smooth_l1",
-           "syn_bn_finalize", "syn_bn_apply2", "syn_bn_block_bwd", "syn_conv1d_train_fwd_norm", "syn_conv1d_train_wgrad_norm", "syn_conv1d_first_tiles",
-           "syn_conv1d_first_fwd_stats", "syn_test_mfma_rate", "syn_conv1d_train_dgrad_sum", "syn_conv1d_first_fwd2", "syn_conv1d_first_wgrad_bn",
-           "syn_bn_bwd_stats", "syn_train_stack_fwd", "syn_train_stack_bwd", "syn_train_stack_wgrad",
-           "syn_masked_smooth_l1_grad", "syn_rows_concat_bf16", "syn_embed_rows_bf16", "syn_bct_to_rows_bf16", "syn_rows_group_sum", "syn_rows_expand",
-           "syn_colsum_parts", "syn_touch", "syn_conv1d_wgrad_sums", "syn_bn_finalize_pair", "syn_conv1d_train_fwd_pair",
-           "syn_tmr_pack_weight", "syn_tmr_encode", "syn_bert_encode", "syn_skel_pack_weight", "syn_skel_encode",
-           "syn_t2m_pack_weight", "syn_t2m_workspace_bytes", "syn_t2m_encode_motion", "syn_t2m_encode_text",
-           "syn_vq_train_pack", "syn_vq_train_cast", "syn_vq_train_ew", "syn_vq_train_pairsum", "syn_vq_train_stuff", "syn_vq_train_wgrad",
-           "syn_vq_train_codebook_prep", "syn_vq_train_tile", "syn_vq_train_quantize", "syn_vq_train_codebook_update",
-           "syn_vq_train_loss_parts", "syn_vq_train_loss", "syn_vq_train_scalars", "syn_plms_update", "syn_bpd_terms",
-           "syn_guide_in_fwd", "syn_guide_in_bwd", "syn_guide_update",
-           "syn_fk_joints", "syn_joint_speed", "syn_motion_beats", "syn_beat_align", "syn_l1div_workspace_bytes", "syn_l1div", "syn_recover_from_ric",
-           "syn_mesh_pack_dirs", "syn_fk_transforms", "syn_mesh_vertices", "syn_vertex_losses_workspace_bytes", "syn_vertex_losses")
-
-# the `void syn_debug_*` switches of the header's diagnostics section (process-wide, A/B runs and scripts/ only)
-DIAGNOSTICS = ("syn_debug_timing", "syn_debug_gemm_resident", "syn_debug_linear_tile", "syn_debug_conv_terms", "syn_debug_seq_skew", "syn_debug_seq_step")
-
 vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 
 
@@ -215,6 +193,47 @@ class SynHipError(RuntimeError):
     pass
 
 
+# ---- the ctypes signatures, read from the prototypes of include/syn_hip.h (the header is the contract; nothing is bound by hand) ----
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_RETURNS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p, "void": None}
+_MIRRORS = {n.lower(): c for n, c in list(globals().items()) if isinstance(c, type) and issubclass(c, C.Structure)}    # "synvqmodel" -> SynVqModel
+# struct pointers that stay c_void_p: callers pass a device address (the tables, the job array) or a cast ctypes array (the requests) there
+_RAW_STRUCT_POINTERS = {("syn_plms_update", "table"), ("syn_bpd_terms", "table"), ("syn_pack_weights", "jobs_dev"), ("syn_conv1d_pack_split_many", "reqs")}
+
+
+def prototypes(header_text):
+    """{name: (restype, argtypes)} of every `<ret> syn_name(<params>);` in the header.  Scalars map by width, a pointer to a syn_* struct to
+    POINTER(its mirror above), every other pointer to c_void_p; a type outside that raises SynHipError naming the function - nothing is ever
+    left to ctypes' default (which passes a 64-bit count or pointer as a C int)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^[ \t]*([\w \t*]+?)\s*\b(syn_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        ret = " ".join(ret.split()).replace(" *", "*")
+        if ret not in _RETURNS:
+            raise SynHipError(f"include/syn_hip.h: {name} returns `{ret}`, which the ctypes binding cannot map")
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(?:const\s+)?([\w ]+?)\s*(\**)\s*(\w+)\s*", p)
+            base, stars, pname = m.groups() if m else (p, "", "")
+            if base.startswith("syn_") and (name, pname) not in _RAW_STRUCT_POINTERS:
+                base = _MIRRORS.get(base.replace("_", ""))            # None: a struct without a mirror
+            if stars == "*" and isinstance(base, type):
+                argtypes.append(C.POINTER(base))
+            elif stars and (base in _SCALARS or base in ("void", "uint8_t", "uint32_t", "long long") or (name, pname) in _RAW_STRUCT_POINTERS):
+                argtypes.append(C.c_void_p)
+            elif not stars and base in _SCALARS:
+                argtypes.append(_SCALARS[base])
+            else:
+                raise SynHipError(f"include/syn_hip.h: {name} takes `{' '.join(p.split())}`, which the ctypes binding cannot map")
+        out[name] = (_RETURNS[ret], argtypes)
+    return out
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = prototypes(_f.read())
+EXPORTS = tuple(n for n in PROTOTYPES if not n.startswith("syn_debug_"))
+DIAGNOSTICS = tuple(n for n in PROTOTYPES if n.startswith("syn_debug_"))      # the process-wide `void syn_debug_*` switches (A/B runs and scripts/ only)
+
 _lib = None
 
 
@@ -228,164 +247,17 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback for the denoising path.")
     lib = C.CDLL(LIB_PATH)
-    lib.syn_version.restype = C.c_int
-    if lib.syn_version() != ABI_VERSION:
+
+    def bind(name):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = PROTOTYPES[name]
+        return fn
+
+    if bind("syn_version")() != ABI_VERSION:
         raise SynHipError(f"{LIB_PATH} has ABI version {lib.syn_version()}, this package needs {ABI_VERSION}: rebuild it "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-    lib.syn_last_error.restype = C.c_char_p
-    lib.syn_denoise_step.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), vp]
-    lib.syn_denoise_step_edit.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), C.POINTER(SynEdit), vp]
-    lib.syn_denoise_steps.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.syn_denoise_step_profile.argtypes = [C.POINTER(SynModel), C.POINTER(SynStep), vp, vp, vp]
-    lib.syn_pack_weight.argtypes = [vp, i32, i32, vp, vp]
-    lib.syn_pack_weight_t.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.syn_to_token_major.argtypes = [vp, i32, vp, vp, vp]
-    lib.syn_from_token_major.argtypes = [vp, i32, vp, vp]
-    lib.syn_x_to_fragment.argtypes = [vp, i32, vp, vp, vp]
-    lib.syn_x_from_fragment.argtypes = [vp, i32, vp, vp]
-    lib.syn_prefers_fragment_order.argtypes = [i32, i32]
-    lib.syn_axpby_rows.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
-    lib.syn_randn.argtypes = [vp, i64, u64, u64, i64, vp]
-    lib.syn_linear.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
-    lib.syn_linear_and_pack.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.syn_linear_pair.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]
-    lib.syn_linear_res.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_linear_gelu.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    f32 = C.c_float
-    lib.syn_conv1d_pack_split_many.argtypes = [vp, i32, vp]
-    lib.syn_opt_blocks.argtypes = [C.POINTER(SynOptList)]
-    lib.syn_opt_blocks.restype = i32
-    lib.syn_opt_sqnorm.argtypes = [C.POINTER(SynOptList), vp, vp]
-    lib.syn_opt_scalars.argtypes = [vp, i32, f32, vp, f32, f32, f32, vp, vp, vp]
-    lib.syn_opt_adam.argtypes = [C.POINTER(SynOptList), vp, f32, f32, f32, f32, vp]
-    lib.syn_test_gemm.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.syn_test_attention.argtypes = [vp, vp, vp, i32, vp, vp]
-    lib.syn_test_handoff.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, vp]
-    lib.syn_step_advance.argtypes = [vp, vp, vp, i32, vp, i32, vp]
-    lib.syn_steps_advance.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp]
-    lib.syn_ln_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.syn_ln_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.syn_gelu_fwd.argtypes = [vp, vp, vp, i64, vp]
-    lib.syn_gelu_bwd.argtypes = [vp, vp, vp, i64, vp]
-    lib.syn_linear_wgrad_rows.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.syn_masked_smooth_l1.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.syn_masked_smooth_l1_grad.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_rows_concat_bf16.argtypes = [C.POINTER(SynConcatSrc), i32, i32, i32, vp, vp]
-    lib.syn_embed_rows_bf16.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.syn_bct_to_rows_bf16.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.syn_rows_group_sum.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.syn_rows_expand.argtypes = [vp, i32, i32, i32, C.c_float, i32, vp, vp]
-    lib.syn_colsum_parts.argtypes = [vp, i32, i32, vp, vp]
-    lib.syn_touch.argtypes = [vp, i64, vp]
-    lib.syn_conv1d_wgrad_sums.argtypes = [C.POINTER(SynWgradSumJob), i32, vp]
-    lib.syn_conv1d_train_fwd_pair.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.syn_bn_finalize_pair.argtypes = [C.POINTER(SynBnFinalizeJob), C.POINTER(SynBnFinalizeJob), vp]
-    lib.syn_rotary.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    lib.syn_axis_angle_to_rot6d.argtypes = [vp, i64, vp, vp]
-    lib.syn_rot6d_to_axis_angle.argtypes = [vp, i64, vp, vp]
-    lib.syn_debug_conv_terms.argtypes = [i32]
-    lib.syn_debug_conv_terms.restype = None
-    lib.syn_attn_fwd.argtypes = [vp, vp, vp, i32, vp]
-    lib.syn_attn_bwd.argtypes = [vp, vp, vp, i32, vp]
-    lib.syn_wav_encode.argtypes = [C.POINTER(SynWavEnc), vp, i32, i32, vp, vp, vp]
-    lib.syn_cond_encode.argtypes = [C.POINTER(SynCondWeights), vp, vp, vp, vp, i32, vp, vp, vp]
-    lib.syn_bn_chunks.argtypes = [C.c_int64]
-    lib.syn_bn_act_fwd.argtypes = [vp, vp, C.c_int64, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp, i32, vp, i32, vp, vp, vp]
-    lib.syn_bn_act_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp, vp]
-    lib.syn_bn_sums.argtypes = [vp, C.c_int64, i32, vp, i32, vp, vp]
-    lib.syn_bn_act_apply.argtypes = [vp, vp, C.c_int64, C.c_int64, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.syn_bn_bwd_sums.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp]
-    lib.syn_bn_act_bwd_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, i32, i32, vp, vp, vp, vp, vp]
-    lib.syn_bn_finalize.argtypes = [vp, i32, C.c_int64, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]
-    lib.syn_bn_apply2.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp]
-    lib.syn_bn_block_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.syn_conv1d_train_fwd_norm.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]
-    lib.syn_conv1d_train_wgrad_norm.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
-    lib.syn_conv1d_first_tiles.argtypes = [i32, i32]
-    lib.syn_conv1d_first_fwd_stats.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.syn_test_mfma_rate.argtypes = [i32, vp, vp, vp]
-    lib.syn_train_stack_fwd.argtypes = [C.POINTER(SynTrainStack), vp]
-    lib.syn_train_stack_bwd.argtypes = [C.POINTER(SynTrainStackGrad), vp]
-    lib.syn_train_stack_wgrad.argtypes = [C.POINTER(SynTrainStackGrad), vp]
-    lib.syn_conv1d_first_fwd2.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.syn_conv1d_first_wgrad_bn.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_first_wgrad_tail.argtypes = [vp] * 10 + [i32] * 6 + [vp, vp, vp]
-    lib.syn_conv1d_first_wgrad_bn_lin.argtypes = [vp] * 5 + [i32] * 6 + [vp, vp, vp, vp]
-    lib.syn_bn_bwd_stats.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_train_dgrad_sum.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.syn_linear_bwd_prep.argtypes = [vp, i32, i32, C.c_float, i32, i32, vp, i32, vp, vp, vp, vp]
-    lib.syn_pack_weights.argtypes = [vp, i32, C.c_int64, vp]
-    lib.syn_embedding_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.syn_conv1d_train_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_wgrad_shares.argtypes = [i32, i32, i32, i32]
-    lib.syn_conv1d_train_wgrad_pair.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.syn_conv1d_first_parts.argtypes = [i32, i32]
-    lib.syn_conv1d_first_fwd.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_first_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_pack_bytes.argtypes = [i32, i32, i32, i32]
-    lib.syn_conv1d_pack_split.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_conv1d_train_fwd.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]
-    lib.syn_conv1d_train_fwd_tiles.argtypes = [i32, i32, i32, i32, i32, i32]
-    lib.syn_wav_workspace_bytes.argtypes = [i32, i32]
-    lib.syn_wav_out_frames.argtypes = [i32]
-    lib.syn_vq_conv1d.argtypes = [C.POINTER(SynVqConv), vp, vp, vp, i32, vp, i32, i32, i32, vp]
-    lib.syn_vq_quantize_groups.argtypes = [i32]
-    lib.syn_vq_quantize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.syn_vq_codes.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    lib.syn_vq_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.syn_vq_map2latent.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, vp, vp, vp]
-    lib.syn_vq_latent2origin.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.syn_vq_forward_decoder.argtypes = [C.POINTER(SynVqModel), vp, i32, i32, i32, vp, vp, vp]
-    lib.syn_tmr_pack_weight.argtypes = [vp, i32, i32, vp, vp]
-    lib.syn_tmr_encode.argtypes = [C.POINTER(SynTmrModel), vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.syn_bert_encode.argtypes = [C.POINTER(SynBertModel), vp, i32, i32, vp, vp, vp, vp]
-    lib.syn_skel_pack_weight.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    lib.syn_skel_encode.argtypes = [C.POINTER(SynSkelModel), vp, i32, i32, vp, vp, vp]
-    lib.syn_t2m_pack_weight.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.syn_t2m_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.syn_t2m_encode_motion.argtypes = [C.POINTER(SynT2mModel), vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.syn_t2m_encode_text.argtypes = [C.POINTER(SynT2mModel), vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.syn_vq_train_pack.argtypes = [vp, i32, i32, vp]
-    lib.syn_vq_train_cast.argtypes = [vp, i64, i32, i32, vp, vp, vp]
-    lib.syn_vq_train_ew.argtypes = [vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, i64, vp]
-    lib.syn_vq_train_pairsum.argtypes = [vp, vp, i64, i32, vp]
-    lib.syn_vq_train_stuff.argtypes = [vp, vp, i64, i32, vp]
-    lib.syn_vq_train_wgrad.argtypes = [vp, i32, vp, i32, vp, vp] + [i32] * 11 + [vp]
-    lib.syn_vq_train_codebook_prep.argtypes = [vp, vp, vp, vp]
-    lib.syn_vq_train_tile.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-    lib.syn_vq_train_quantize.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.syn_vq_train_codebook_update.argtypes = [vp, vp, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp]
-    lib.syn_vq_train_loss_parts.argtypes = [i64, i32]
-    lib.syn_vq_train_loss.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp]
-    lib.syn_vq_train_scalars.argtypes = [vp, i32, i64, vp, i32, vp, i32, i32, f32, vp, vp]
-    lib.syn_plms_update.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
-    lib.syn_bpd_terms.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
-    lib.syn_guide_in_fwd.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
-    lib.syn_guide_in_bwd.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
-    lib.syn_guide_update.argtypes = [i32, vp, vp, vp, vp, i32, u64, u64, vp, i32, vp, i32, vp, vp]
-    lib.syn_fk_joints.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, i64, vp, vp, vp]
-    lib.syn_joint_speed.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp]
-    lib.syn_motion_beats.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
-    lib.syn_beat_align.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, C.c_double, f32, vp, vp, vp]
-    lib.syn_l1div_workspace_bytes.argtypes = [i32, i64, i32]
-    lib.syn_l1div.argtypes = [vp, i32, i64, i32, vp, i32, vp, vp]
-    lib.syn_recover_from_ric.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.syn_mesh_pack_dirs.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    lib.syn_fk_transforms.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, vp, vp]
-    lib.syn_mesh_vertices.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, i64, vp, vp]
-    lib.syn_vertex_losses_workspace_bytes.argtypes = [i64, i32]
-    lib.syn_vertex_losses.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
-    for name in EXPORTS:
-        fn = getattr(lib, name)
-        if name not in ("syn_version", "syn_last_error", "syn_wav_workspace_bytes", "syn_vq_workspace_bytes", "syn_conv1d_pack_bytes",
-                        "syn_t2m_workspace_bytes", "syn_l1div_workspace_bytes", "syn_vertex_losses_workspace_bytes"):
-            fn.restype = C.c_int
-    lib.syn_wav_workspace_bytes.restype = C.c_int64
-    lib.syn_conv1d_pack_bytes.restype = C.c_int64
-    lib.syn_vq_workspace_bytes.restype = C.c_int64
-    lib.syn_t2m_workspace_bytes.restype = C.c_int64
-    lib.syn_l1div_workspace_bytes.restype = C.c_int64
-    lib.syn_vertex_losses_workspace_bytes.restype = C.c_int64
+    for name in PROTOTYPES:
+        bind(name)
     _lib = lib
     return lib
 

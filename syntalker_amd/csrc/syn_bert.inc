@@ -5,6 +5,7 @@
 // row of A and writes no invalid row.  Every Linear is one launch of k_bert_gemm (k_tmr_gemm's tile and hi + lo bf16 split: 64 rows x 256
 // columns, three MFMAs per product) with bias, bias + GELU or bias + residual; a LayerNorm is its own launch (k_bert_ln, a wave per row);
 // attention is k_bert_attn (a workgroup per sequence, head and 64 queries) with hi + lo bf16 splits of Q, K, P and V as well.
+namespace {
 namespace bert {
 
 using tmr::kArow;
@@ -308,8 +309,12 @@ int gemm(const GemmArgs& a, int n_cols, hipStream_t st) {
     return launched("k_bert_gemm launch");
 }
 
-static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
-                  float* hidden, void* stream) {
+}  // namespace bert
+}  // namespace
+
+extern "C" int syn_bert_encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                    float* hidden, void* stream) {
+    using namespace bert;
     if (!m || !ids || !workspace || !hidden) return fail_msg("syn_bert_encode: null pointer");
     if (n_seq < 1 || n_seq > SYN_TMR_MAX_SEQ || max_len < 1 || max_len > SYN_TMR_MAX_LEN)
         return fail_msg("syn_bert_encode: n_seq outside 1 .. SYN_TMR_MAX_SEQ or max_len outside 1 .. SYN_TMR_MAX_LEN");
@@ -356,7 +361,7 @@ static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, in
                            (const float*)nullptr, 0, lengths, (int)max_len, R, y.ln1_g, y.ln1_b, x);
         if ((rc = launched("k_bert_ln launch"))) return rc;
         g.a = x; g.w = (const bf16x8*)y.w_fc1; g.n_frag_cols = kFF / 16; g.bias = y.b_fc1; g.res = nullptr; g.out = hid; g.ld_out = kFF;  // lin1 + GELU
-        if ((rc = gemm<EPI_GELU>(g, kFF, st))) return rc;
+        if ((rc = gemm<bert::EPI_GELU>(g, kFF, st))) return rc;
         g.a = hid; g.lda = kFF; g.KS = kFF / kKC; g.w = (const bf16x8*)y.w_fc2; g.n_frag_cols = kD / 16; g.bias = y.b_fc2; g.res = x; g.out = tmp;
         g.ld_out = kD;                                          // lin2 + residual
         if ((rc = gemm<EPI_RES>(g, kD, st))) return rc;
@@ -366,4 +371,3 @@ static int encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, in
     }
     return 0;
 }
-}  // namespace bert

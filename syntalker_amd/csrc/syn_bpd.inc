@@ -19,6 +19,7 @@
 // (shuffles) and the workgroup (LDS).  Integer addition is associative, so the result does not depend on which thread met which group: no
 // atomics, bitwise the same on every run, in every launch and for every order of the groups - token-major and fragment-order latents (the
 // same 16-byte groups, permuted) give the same bits.  What lies below 2^-96 is dropped; a group sum of 2^32 or more gives +inf, a NaN NaN.
+namespace {
 namespace bpd {
 
 constexpr int kSeq4 = 32 * 1536 / 4;          // 16-byte groups per sequence
@@ -146,8 +147,11 @@ __global__ __launch_bounds__(kThreads) void k_bpd_terms(const syn_bpd_row* __res
     }
 }
 
-static int terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
-                 const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream) {
+}  // namespace bpd
+}  // namespace
+
+extern "C" int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
+                             const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream) {
     if (!table || n_rows <= 0 || !t_row || !x_start || n_clips <= 0 || !x_t || !noise || !pred_x0 || n_seq <= 0 || !out)
         return fail_msg("syn_bpd_terms: null pointer, empty table, or no clips / sequences");
     if (!clip && n_seq > n_clips) return fail_msg("syn_bpd_terms: clip = NULL pairs sequence i with clip i: n_seq must not exceed n_clips");
@@ -155,10 +159,8 @@ static int terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row,
         return fail_msg("syn_bpd_terms: x_start, x_t, noise and pred_x0 must be 16-byte aligned");
     if (((uintptr_t)table | (uintptr_t)t_row | (uintptr_t)clip | (uintptr_t)out) & 3)
         return fail_msg("syn_bpd_terms: table, t_row, clip and out must be 4-byte aligned");
-    hipLaunchKernelGGL(k_bpd_terms, dim3((unsigned)n_seq), dim3(kThreads), 0, (hipStream_t)stream, table, (int)n_rows, (const int*)t_row,
+    hipLaunchKernelGGL(bpd::k_bpd_terms, dim3((unsigned)n_seq), dim3(bpd::kThreads), 0, (hipStream_t)stream, table, (int)n_rows, (const int*)t_row,
                        (const int*)clip, (const f32x4*)x_start, (int)n_clips, (const f32x4*)x_t, (const f32x4*)noise, (const f32x4*)pred_x0,
                        (int)n_seq, out);
     return launched("k_bpd_terms launch");
 }
-
-}  // namespace bpd

@@ -8,6 +8,7 @@
 // with GT = (W2c Wm_a)^T (256 x 512), TW = word_embedding (W2c Wm_w Wt)^T (vocabulary x 512: the whole word path is a
 // table lookup), ST = [W2a W_embed_text | W3s]^T.  fp32 FMA kernels (15 MFLOP per clip; the result feeds every step, so it
 // keeps fp32), weights read coalesced along n, activations broadcast from LDS.
+namespace {
 namespace cnd {
 
 // d[b][n] as kClipSplit partial sums over K: 32 clips x 64 features x one K share per workgroup (a thread = one feature x 8 clips:
@@ -87,3 +88,24 @@ __global__ __launch_bounds__(256) void k_cond_frames(const float* __restrict__ a
 }
 
 }  // namespace cnd
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_cond_encode(const syn_cond_weights* w, const float* audio_feat, const int64_t* word, const float* seed, const float* style,
+                    int32_t n_clips, float* d_scratch, float* cond, void* stream) {
+    if (!w || !w->gt || !w->tw || !w->st || !w->c0 || !audio_feat || !word || !seed || !d_scratch || !cond || n_clips <= 0)
+        return fail_msg("syn_cond_encode: null argument");
+    if (w->seed_dim <= 0 || w->style_dim < 0 || w->vocab <= 0 || (w->style_dim > 0 && !style))
+        return fail_msg("syn_cond_encode: bad dimensions (a model with a style projection needs the style vectors)");
+    hipStream_t s = (hipStream_t)stream;
+    static_assert(cnd::kClipSplit == SYN_COND_SCRATCH_ROWS, "include/syn_hip.h: d_scratch rows per clip");
+    hipLaunchKernelGGL(cnd::k_cond_clip, dim3(SYN_D / 64, (n_clips + 31) / 32, cnd::kClipSplit), dim3(256), 0, s, seed, w->seed_dim, style,
+                       w->style_dim, w->st, n_clips, d_scratch);
+    hipLaunchKernelGGL(cnd::k_cond_frames, dim3(SYN_D / 128, n_clips), dim3(256), 0, s, audio_feat, (const long long*)word, w->gt, w->tw,
+                       w->vocab, d_scratch, w->c0, n_clips, cond);
+    return launched("syn_cond_encode");
+}
+
+}  // extern "C"

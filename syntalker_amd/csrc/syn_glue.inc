@@ -4,8 +4,9 @@
 // ~90 launches of 2-15 us per step (0.36 ms of a 4.6 ms step, profiles/r05_train_step_split.txt).  Every kernel here writes a GEMM
 // operand in the form the GEMM takes it (bf16 rows, zero-padded to the 128-column granularity) or reads a gradient where the GEMM left it
 // (a column slice of a wider fp32 tensor), so no cast, cat, pad, slice copy or transpose launch is left.  All HBM-bound elementwise work:
-// one pass, coalesced 16-byte accesses.  Included by syn_kernels.hip.
+// one pass, coalesced 16-byte accesses.  Included by syn_kernels.hip; entry points at the end.
 
+namespace {
 namespace glu {
 
 // ---- bf16 GEMM operand [M][out_ld] = the concatenation of up to 4 fp32 sources along the columns (+ zero padding) ---------------------------
@@ -247,3 +248,97 @@ __global__ __launch_bounds__(kEmbWaves * 64) void k_embedding_wgrad(const long* 
 }
 
 }  // namespace glu
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_masked_smooth_l1(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
+                         float* part, const int32_t* poison_flag, float* loss, void* stream) {
+    if (!target || !out || !mask || !loss || !part || batch <= 0 || channels <= 0 || channels % 64 || t_len <= 0 || t_len > 64)
+        return fail_msg("syn_masked_smooth_l1: channels must be a multiple of 64, t_len <= 64, part [batch][channels / 64]");
+    const int chunks = channels / 64;
+    hipLaunchKernelGGL(glu::k_sl1_tiles<false>, dim3(chunks, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
+                       (const float*)nullptr, part, (float*)nullptr);
+    hipLaunchKernelGGL(glu::k_sl1_final, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, mask, batch, chunks, channels, t_len, poison_flag, loss);
+    return launched("k_sl1_tiles launch");
+}
+
+int syn_masked_smooth_l1_grad(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
+                              const float* sample_scale, float* dout, void* stream) {
+    if (!target || !out || !mask || !dout || batch <= 0 || channels <= 0 || channels % 64 || t_len <= 0 || t_len > 64)
+        return fail_msg("syn_masked_smooth_l1_grad: channels must be a multiple of 64, t_len <= 64");
+    hipLaunchKernelGGL(glu::k_sl1_tiles<true>, dim3(channels / 64, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
+                       sample_scale, (float*)nullptr, dout);
+    return launched("k_sl1_tiles (gradient) launch");
+}
+
+int syn_rows_concat_bf16(const syn_concat_src* srcs, int32_t n_src, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
+    if (!srcs || n_src < 1 || n_src > SYN_CONCAT_MAX || m_rows <= 0 || out_ld <= 0 || out_ld % 4 || !out_bf16) return fail_msg("syn_rows_concat_bf16: 1 .. 4 sources, out_ld % 4 == 0");
+    glu::CatArgs a;
+    memset(&a, 0, sizeof(a));
+    int total = 0;
+    for (int i = 0; i < n_src; ++i) {
+        const syn_concat_src& c = srcs[i];
+        if (!c.p || c.width <= 0 || c.width % 4 || c.ld % 4 || c.ld < c.width || c.row_div < 1 || c.pool < 1 || (c.pool > 1 && (c.row_div != 1 || c.p2)))
+            return fail_msg("syn_rows_concat_bf16: a source needs width % 4 == 0, ld % 4 == 0, ld >= width, row_div >= 1, pool >= 1 (a pooled source: row_div 1, no addend)");
+        a.s[i].p = c.p; a.s[i].p2 = c.p2; a.s[i].width = c.width; a.s[i].ld = c.ld; a.s[i].row_div = c.row_div; a.s[i].pool = c.pool;
+        total += c.width;
+    }
+    if (total > out_ld) return fail_msg("syn_rows_concat_bf16: the sources are wider than out_ld");
+    a.n_src = n_src; a.M = m_rows; a.out_ld = out_ld; a.out = (__bf16*)out_bf16;
+    const long n = (long)m_rows * (out_ld / 4);
+    hipLaunchKernelGGL(glu::k_rows_concat_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launched("k_rows_concat_bf16 launch");
+}
+
+int syn_embed_rows_bf16(const int64_t* ids, const float* table, int32_t vocab, int32_t dim, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
+    if (!ids || !table || !out_bf16 || vocab <= 0 || dim <= 0 || dim % 4 || m_rows <= 0 || out_ld < dim || out_ld % 4) return fail_msg("syn_embed_rows_bf16: dim % 4 == 0, out_ld >= dim, out_ld % 4 == 0");
+    const long n = (long)m_rows * (out_ld / 4);
+    hipLaunchKernelGGL(glu::k_embed_rows_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long*>(ids), table, vocab,
+                       dim, m_rows, out_ld, (__bf16*)out_bf16);
+    return launched("k_embed_rows_bf16 launch");
+}
+
+int syn_bct_to_rows_bf16(const float* x_bct, int32_t n_clips, int32_t channels, int32_t t_len, void* out_bf16, void* stream) {
+    if (!x_bct || !out_bf16 || n_clips <= 0 || channels <= 0 || channels % 64 || t_len != 32) return fail_msg("syn_bct_to_rows_bf16: channels % 64 == 0, t_len == 32");
+    hipLaunchKernelGGL(glu::k_bct_to_rows_bf16, dim3(channels / 64, n_clips), dim3(256), 0, (hipStream_t)stream, x_bct, channels, (__bf16*)out_bf16);
+    return launched("k_bct_to_rows_bf16 launch");
+}
+
+int syn_rows_group_sum(const float* src, int32_t ld, int32_t width, int32_t group, int32_t n_groups, float* out, void* stream) {
+    if (!src || !out || ld < width || width <= 0 || group <= 0 || n_groups <= 0) return fail_msg("syn_rows_group_sum: bad arguments");
+    hipLaunchKernelGGL(glu::k_rows_group_sum, dim3((n_groups * width + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, ld, width, group, n_groups, out);
+    return launched("k_rows_group_sum launch");
+}
+
+int syn_rows_expand(const float* src, int32_t ld, int32_t width, int32_t row_div, float scale, int32_t m_rows, float* out, void* stream) {
+    if (!src || !out || width <= 0 || width % 4 || ld < width || ld % 4 || row_div < 1 || m_rows <= 0) return fail_msg("syn_rows_expand: width % 4 == 0, ld >= width, ld % 4 == 0, row_div >= 1");
+    const long n = (long)m_rows * (width / 4);
+    hipLaunchKernelGGL(glu::k_rows_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, ld, width, row_div, scale, m_rows, out);
+    return launched("k_rows_expand launch");
+}
+
+int syn_colsum_parts(const float* part, int32_t rows, int32_t n, float* out, void* stream) {
+    if (!part || !out || rows <= 0 || n <= 0) return fail_msg("syn_colsum_parts: bad arguments");
+    hipLaunchKernelGGL(glu::k_colsum_parts, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, part, rows, n, out);
+    return launched("k_colsum_parts launch");
+}
+
+int syn_touch(const void* p, int64_t bytes, void* stream) {
+    if (!p || bytes < 64) return fail_msg("syn_touch: at least one 64-byte line");
+    const long lines = bytes / 64;
+    const long blocks = (lines + 255) / 256;
+    hipLaunchKernelGGL(glu::k_touch, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)p, lines, (unsigned*)nullptr);
+    return launched("k_touch launch");
+}
+
+int syn_embedding_wgrad(const int64_t* ids, const float* dy, int32_t ld, int32_t n_pos, int32_t vocab, int32_t dim, float* dw, void* stream) {
+    if (!ids || !dy || !dw || n_pos <= 0 || n_pos > glu::kEmbMaxPos || vocab <= 0 || vocab > glu::kEmbMaxV || dim <= 0 || dim > glu::kEmbMaxD || ld < dim)
+        return fail_msg("syn_embedding_wgrad: bad arguments (at most 8192 positions per call, vocab <= 65536, dim <= 512, ld >= dim)");
+    hipLaunchKernelGGL(glu::k_embedding_wgrad, dim3((n_pos + glu::kEmbWaves - 1) / glu::kEmbWaves), dim3(glu::kEmbWaves * 64), 0, (hipStream_t)stream,
+                       reinterpret_cast<const long*>(ids), dy, ld, n_pos, vocab, dim, dw);
+    return launched("k_embedding_wgrad launch");
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 //                    so that a lane holds four consecutive frames of one channel, and dx (B, C, 1, T) is written (or added to) with 16-byte stores.
 // One workgroup per sequence (32 rows) and 512 output columns; the sequence's rows stay in the LDS for the whole K loop: `staged_prime` / `staged_loop`, the
 // very loop gemm_mainloop_resident runs, behind loaders of their own.  No atomics: a dx element has one owner, `accumulate` is a read-modify-write by that owner.
+namespace {
 namespace guide {
 
 constexpr int kRows = 32;                 // rows of a workgroup: one sequence
@@ -182,8 +183,13 @@ __global__ __launch_bounds__(256) void k_guide_update(const Upd u) {
     for (int e = 0; e < 4; ++e) u.out[off + e * SYN_T] = r[e];
 }
 
-static int in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const float* cond, const float* te, int32_t n_te, const int32_t* t_model,
-                  const float* rot_cos, const float* rot_sin, int32_t n_live, int32_t n_seq, float* h0, void* stream) {
+}  // namespace guide
+}  // namespace
+
+extern "C" {
+
+int syn_guide_in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const float* cond, const float* te, int32_t n_te, const int32_t* t_model,
+                     const float* rot_cos, const float* rot_sin, int32_t n_live, int32_t n_seq, float* h0, void* stream) {
     if (!x_bct || !a_packed || !cond || !te || !t_model || !rot_cos || !rot_sin || !h0 || n_te <= 0)
         return fail_msg("syn_guide_in_fwd: null pointer or empty time table");
     if (n_seq < 1 || n_seq > 65535 || n_live < 1 || n_live > n_seq || n_x < 1 || n_x > n_live)
@@ -191,36 +197,36 @@ static int in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const f
     if (((uintptr_t)x_bct | (uintptr_t)cond | (uintptr_t)te | (uintptr_t)rot_cos | (uintptr_t)rot_sin | (uintptr_t)h0 | (uintptr_t)a_packed) & 15)
         return fail_msg("syn_guide_in_fwd: operands must be 16-byte aligned");
     static OncePerDevice once;
-    if (once.first()) { allow_lds(k_guide_in_fwd, kFwdLds); }
-    InFwd a;
+    if (once.first()) { allow_lds(guide::k_guide_in_fwd, guide::kFwdLds); }
+    guide::InFwd a;
     a.x = x_bct; a.n_x = n_x; a.A = (const uint4*)a_packed; a.cond = cond; a.te = te; a.n_te = n_te; a.t_model = (const int*)t_model;
     a.rcos = rot_cos; a.rsin = rot_sin; a.n_live = n_live; a.h0 = h0;
-    hipLaunchKernelGGL(k_guide_in_fwd, dim3(n_seq), dim3(kThreads), kFwdLds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(guide::k_guide_in_fwd, dim3(n_seq), dim3(kThreads), guide::kFwdLds, (hipStream_t)stream, a);
     return launched("k_guide_in_fwd launch");
 }
 
-static int in_bwd(const float* dh0, const void* at_packed, const float* rot_cos, const float* rot_sin, int32_t n_seq, int32_t accumulate, float* dx_bct,
-                  void* stream) {
+int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_cos, const float* rot_sin, int32_t n_seq, int32_t accumulate, float* dx_bct,
+                     void* stream) {
     if (!dh0 || !at_packed || !rot_cos || !rot_sin || !dx_bct) return fail_msg("syn_guide_in_bwd: null pointer");
     if (n_seq < 1 || n_seq > 65535) return fail_msg("syn_guide_in_bwd: 1 <= n_seq <= 65535");
     if (((uintptr_t)dh0 | (uintptr_t)at_packed | (uintptr_t)rot_cos | (uintptr_t)rot_sin | (uintptr_t)dx_bct) & 15)
         return fail_msg("syn_guide_in_bwd: operands must be 16-byte aligned");
-    InBwd a;
+    guide::InBwd a;
     a.dh0 = dh0; a.At = (const uint4*)at_packed; a.rcos = rot_cos; a.rsin = rot_sin; a.dx = dx_bct; a.accumulate = accumulate != 0;
-    hipLaunchKernelGGL(k_guide_in_bwd, dim3(n_seq, SYN_C / kNT), dim3(kThreads), kBwdLds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(guide::k_guide_in_bwd, dim3(n_seq, SYN_C / kNT), dim3(kThreads), guide::kBwdLds, (hipStream_t)stream, a);
     return launched("k_guide_in_bwd launch");
 }
 
-static int update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed, uint64_t first_clip,
-                  const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream) {
+int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
+                     uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream) {
     if (!a || !grad || !coef || !t_idx || !out || n_rows <= 0 || n_clips <= 0 || mode < 0 || mode > 1 || (mode == 1 && !pred_x0))
         return fail_msg("syn_guide_update: null pointer, empty table or batch, or a mode other than 0 (mean) / 1 (score, which needs pred_x0)");
-    Upd u;
+    guide::Upd u;
     u.mode = mode; u.a = a; u.x0 = pred_x0; u.g = grad; u.noise = noise; u.draw = draw != 0; u.seed = seed; u.first_clip = first_clip;
     u.coef = coef; u.n_rows = n_rows; u.t_idx = (const int*)t_idx; u.n_clips = n_clips; u.out = out;
     const long n = (long)n_clips * (SYN_C / 4) * SYN_T;
-    hipLaunchKernelGGL(k_guide_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u);
+    hipLaunchKernelGGL(guide::k_guide_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u);
     return launched("k_guide_update launch");
 }
 
-}  // namespace guide
+}  // extern "C"

@@ -6,6 +6,7 @@
 // What SMPL-X contributes to the metrics is `joints[:, :55]`: forward kinematics over the 55-joint tree from the rest joints of the shaped
 // template (the joints are regressed before the pose correctives, and `test()` passes zero expression and zero transl).  The rest joints are
 // one host product per subject (joints.smplx_rest_joints); the kernel below is the tree walk.
+namespace {
 namespace joints {
 
 constexpr int kMaxJ = 64;              // joints of a tree
@@ -427,70 +428,75 @@ __global__ __launch_bounds__(kRicTile) void k_recover_from_ric(const float* __re
     }
 }
 
+}  // namespace joints
+}  // namespace
+
+extern "C" {
+
 // ---- entry points ------------------------------------------------------------------------------------------------------------------------
-static int fk(const int32_t* parents, int32_t n_joints, const float* rest, int32_t n_takes, const float* rot, int32_t six, const float* transl,
-              const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, const float* pose_mean, float* out, void* stream) {
-    if (!parents || !rest || !rot || !out) return fail_msg("syn_fk_joints: null pointer");
-    if (pose_mean && six) return fail_msg("syn_fk_joints: a mean pose is added to axis-angle vectors; convert 6D rotations first (syn_rot6d_to_axis_angle)");
-    if (n_joints < 1 || n_joints > kMaxJ) return fail_msg("syn_fk_joints: a tree has 1 to 64 joints");
+int syn_fk_joints(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* rot, int32_t rot6d, const float* transl,
+                  const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, const float* pose_mean, float* joints_out, void* stream) {
+    if (!parents || !rest_joints || !rot || !joints_out) return fail_msg("syn_fk_joints: null pointer");
+    if (pose_mean && rot6d) return fail_msg("syn_fk_joints: a mean pose is added to axis-angle vectors; convert 6D rotations first (syn_rot6d_to_axis_angle)");
+    if (n_joints < 1 || n_joints > joints::kMaxJ) return fail_msg("syn_fk_joints: a tree has 1 to 64 joints");
     if (n_takes < 1 || n_frames < 0) return fail_msg("syn_fk_joints: no takes / negative frame count");
     if (!take_of_frame && frames_per_take < 1) return fail_msg("syn_fk_joints: give a frame-to-take index or the frames per take");
     if (!take_of_frame && n_frames > (int64_t)n_takes * frames_per_take) return fail_msg("syn_fk_joints: more frames than n_takes x frames_per_take");
     if (n_frames == 0) return 0;
-    const int64_t blocks = (n_frames + kFkFrames - 1) / kFkFrames;
+    const int64_t blocks = (n_frames + joints::kFkFrames - 1) / joints::kFkFrames;
     if (blocks > 0x7fffffffLL) return fail_msg("syn_fk_joints: too many frames for one launch");
-    hipLaunchKernelGGL(k_fk<false>, dim3((unsigned)blocks), dim3(kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest, (int)n_takes,
-                       rot, (int)(six != 0), transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, out, pose_mean, FkMesh{});
+    hipLaunchKernelGGL(joints::k_fk<false>, dim3((unsigned)blocks), dim3(joints::kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest_joints, (int)n_takes,
+                       rot, (int)(rot6d != 0), transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, joints_out, pose_mean, joints::FkMesh{});
     return launched("k_fk launch");
 }
 
-static int speed(const float* jt, int32_t n_takes, int32_t n, int32_t n_joints, float fps, const float* mmae, float* out, void* stream) {
-    if (!jt || !out) return fail_msg("syn_joint_speed: null pointer");
-    if (n_takes < 1 || n < 2 || n_joints < 1) return fail_msg("syn_joint_speed: a take needs at least 2 frames and 1 joint");
-    const long total = (long)n_takes * n * n_joints;
+int syn_joint_speed(const float* joints_in, int32_t n_takes, int32_t n_frames, int32_t n_joints, float fps, const float* mmae, float* speed, void* stream) {
+    if (!joints_in || !speed) return fail_msg("syn_joint_speed: null pointer");
+    if (n_takes < 1 || n_frames < 2 || n_joints < 1) return fail_msg("syn_joint_speed: a take needs at least 2 frames and 1 joint");
+    const long total = (long)n_takes * n_frames * n_joints;
     if ((total + 255) / 256 > 0x7fffffffL) return fail_msg("syn_joint_speed: too many elements for one launch");
-    hipLaunchKernelGGL(k_joint_speed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, jt, total, (int)n, (int)n_joints, fps, mmae, out);
+    hipLaunchKernelGGL(joints::k_joint_speed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, joints_in, total, (int)n_frames, (int)n_joints, fps, mmae, speed);
     return launched("k_joint_speed launch");
 }
 
-static int beats(const float* vel, int32_t n_takes, int32_t n, int32_t n_joints, int32_t t_start, int32_t t_end, int32_t order, float threshold,
-                 unsigned char* mask, void* stream) {
+int syn_motion_beats(const float* vel, int32_t n_takes, int32_t n_frames, int32_t n_joints, int32_t t_start, int32_t t_end, int32_t order, float threshold,
+                     uint8_t* mask, void* stream) {
     if (!vel || !mask) return fail_msg("syn_motion_beats: null pointer");
-    if (n_takes < 1 || n < 1 || n_joints < 1 || order < 1) return fail_msg("syn_motion_beats: empty input or order < 1");
-    if (t_start < 0 || t_end < t_start || t_end > n) return fail_msg("syn_motion_beats: the slice must satisfy 0 <= t_start <= t_end <= n");
+    if (n_takes < 1 || n_frames < 1 || n_joints < 1 || order < 1) return fail_msg("syn_motion_beats: empty input or order < 1");
+    if (t_start < 0 || t_end < t_start || t_end > n_frames) return fail_msg("syn_motion_beats: the slice must satisfy 0 <= t_start <= t_end <= n");
     const int n_slice = t_end - t_start;
     const long total = (long)n_takes * n_slice * n_joints;
     if (total == 0) return 0;
     if ((total + 255) / 256 > 0x7fffffffL) return fail_msg("syn_motion_beats: too many elements for one launch");
-    hipLaunchKernelGGL(k_motion_beats, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vel, total, (int)n, (int)n_joints, (int)t_start,
+    hipLaunchKernelGGL(joints::k_motion_beats, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vel, total, (int)n_frames, (int)n_joints, (int)t_start,
                        n_slice, (int)order, threshold, mask);
     return launched("k_motion_beats launch");
 }
 
-static int align(const unsigned char* mask, int32_t n_takes, int32_t n_slice, int32_t n_joints, const int32_t* upper, int32_t n_upper, const double* onsets,
-                 const int32_t* onset_off, double pose_fps, float sigma, float* per_joint, float* bc, void* stream) {
-    if (!mask || !upper || !onsets || !onset_off || !per_joint || !bc) return fail_msg("syn_beat_align: null pointer");
+int syn_beat_align(const uint8_t* mask, int32_t n_takes, int32_t n_slice, int32_t n_joints, const int32_t* upper_body, int32_t n_upper, const double* onsets,
+                   const int32_t* onset_offsets, double pose_fps, float sigma, float* per_joint, float* bc, void* stream) {
+    if (!mask || !upper_body || !onsets || !onset_offsets || !per_joint || !bc) return fail_msg("syn_beat_align: null pointer");
     if (n_takes < 1 || n_slice < 0 || n_joints < 1 || n_upper < 1) return fail_msg("syn_beat_align: no takes / joints");
-    if (n_slice > kAlignMaxSlice) return fail_msg("syn_beat_align: at most 16000 frames per slice");
+    if (n_slice > joints::kAlignMaxSlice) return fail_msg("syn_beat_align: at most 16000 frames per slice");
     if (!(pose_fps > 0.0) || !(sigma > 0.f)) return fail_msg("syn_beat_align: pose_fps and sigma must be positive");
     if ((uintptr_t)onsets & 7) return fail_msg("syn_beat_align: onsets must be 8-byte aligned");
-    hipLaunchKernelGGL(k_beat_align, dim3((unsigned)(n_takes * n_upper)), dim3(kAlignThreads), (size_t)(n_slice / 2 + 1) * sizeof(double), (hipStream_t)stream, mask, (int)n_slice, (int)n_joints,
-                       (const int*)upper, (int)n_upper, onsets, (const int*)onset_off, pose_fps, sigma, per_joint);
+    hipLaunchKernelGGL(joints::k_beat_align, dim3((unsigned)(n_takes * n_upper)), dim3(joints::kAlignThreads), (size_t)(n_slice / 2 + 1) * sizeof(double), (hipStream_t)stream, mask, (int)n_slice, (int)n_joints,
+                       (const int*)upper_body, (int)n_upper, onsets, (const int*)onset_offsets, pose_fps, sigma, per_joint);
     if (int rc = launched("k_beat_align launch")) return rc;
-    hipLaunchKernelGGL(k_beat_mean, dim3((unsigned)((n_takes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const float*)per_joint, (int)n_takes, (int)n_upper, bc);
+    hipLaunchKernelGGL(joints::k_beat_mean, dim3((unsigned)((n_takes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const float*)per_joint, (int)n_takes, (int)n_upper, bc);
     return launched("k_beat_mean launch");
 }
 
-static int64_t l1div_workspace(int32_t n_takes, int64_t n, int32_t channels) {
+int64_t syn_l1div_workspace_bytes(int32_t n_takes, int64_t n, int32_t channels) {
     if (n_takes < 1 || n < 1 || channels < 1) return -1;                 // (no valid call needs 0 bytes: negative = refused, like an error code)
-    return (int64_t)n_takes * (((n + kL1Rows - 1) / kL1Rows) * channels + 2 * (int64_t)channels) * (int64_t)sizeof(double);
+    return (int64_t)n_takes * (((n + joints::kL1Rows - 1) / joints::kL1Rows) * channels + 2 * (int64_t)channels) * (int64_t)sizeof(double);
 }
 
-static int l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
+int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
     if (!x || !workspace || !out) return fail_msg("syn_l1div: null pointer");
     if (n_takes < 1 || n_takes > 65535 || n < 1 || channels < 1) return fail_msg("syn_l1div: empty input, or more than 65535 takes");
     if (((uintptr_t)workspace | (uintptr_t)out) & 7) return fail_msg("syn_l1div: workspace and out must be 8-byte aligned");
-    const long chunks = (n + kL1Rows - 1) / kL1Rows, total = chunks * channels;
+    const long chunks = (n + joints::kL1Rows - 1) / joints::kL1Rows, total = chunks * channels;
     long grid = (total + 255) / 256;
     if (blocks > 0) grid = blocks;                         // (a diagnostic: the result does not depend on it)
     if (grid > 65536) grid = 65536;
@@ -499,20 +505,21 @@ static int l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, v
     double* col = mean + (long)n_takes * channels;
     const unsigned cgrid = (unsigned)((channels + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_l1_chunks, dim3((unsigned)grid, (unsigned)n_takes), dim3(256), 0, s, x, (long)n, (int)channels, (const double*)nullptr, part);
-    hipLaunchKernelGGL(k_l1_columns, dim3(cgrid, (unsigned)n_takes), dim3(256), 0, s, (const double*)part, chunks, (int)channels, 1.0 / (double)n, mean);
-    hipLaunchKernelGGL(k_l1_chunks, dim3((unsigned)grid, (unsigned)n_takes), dim3(256), 0, s, x, (long)n, (int)channels, (const double*)mean, part);
-    hipLaunchKernelGGL(k_l1_columns, dim3(cgrid, (unsigned)n_takes), dim3(256), 0, s, (const double*)part, chunks, (int)channels, 1.0, col);
-    hipLaunchKernelGGL(k_l1_total, dim3((unsigned)n_takes), dim3(256), 0, s, (const double*)col, (int)channels, out);
+    hipLaunchKernelGGL(joints::k_l1_chunks, dim3((unsigned)grid, (unsigned)n_takes), dim3(256), 0, s, x, (long)n, (int)channels, (const double*)nullptr, part);
+    hipLaunchKernelGGL(joints::k_l1_columns, dim3(cgrid, (unsigned)n_takes), dim3(256), 0, s, (const double*)part, chunks, (int)channels, 1.0 / (double)n, mean);
+    hipLaunchKernelGGL(joints::k_l1_chunks, dim3((unsigned)grid, (unsigned)n_takes), dim3(256), 0, s, x, (long)n, (int)channels, (const double*)mean, part);
+    hipLaunchKernelGGL(joints::k_l1_columns, dim3(cgrid, (unsigned)n_takes), dim3(256), 0, s, (const double*)part, chunks, (int)channels, 1.0, col);
+    hipLaunchKernelGGL(joints::k_l1_total, dim3((unsigned)n_takes), dim3(256), 0, s, (const double*)col, (int)channels, out);
     return launched("k_l1 launches");
 }
 
-static int recover_from_ric(const float* data, int32_t n_seq, int32_t n, int32_t channels, int32_t joints_num, float* out, float* root_quat, void* stream) {
-    if (!data || !out) return fail_msg("syn_recover_from_ric: null pointer");
-    if (n_seq < 1 || n < 1 || joints_num < 1) return fail_msg("syn_recover_from_ric: empty input");
+int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
+                         void* stream) {
+    if (!data || !joints_out) return fail_msg("syn_recover_from_ric: null pointer");
+    if (n_seq < 1 || n_frames < 1 || joints_num < 1) return fail_msg("syn_recover_from_ric: empty input");
     if (channels < 4 + 3 * (joints_num - 1)) return fail_msg("syn_recover_from_ric: the features need 4 + 3 (joints_num - 1) channels");
-    hipLaunchKernelGGL(k_recover_from_ric, dim3((unsigned)n_seq), dim3(kRicTile), 0, (hipStream_t)stream, data, (int)n, (int)channels, (int)joints_num, out, root_quat);
+    hipLaunchKernelGGL(joints::k_recover_from_ric, dim3((unsigned)n_seq), dim3(joints::kRicTile), 0, (hipStream_t)stream, data, (int)n_frames, (int)channels, (int)joints_num, joints_out, root_quat);
     return launched("k_recover_from_ric launch");
 }
 
-}  // namespace joints
+}  // extern "C"

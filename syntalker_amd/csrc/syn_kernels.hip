@@ -26,7 +26,8 @@
 //   D: lane l, reg r holds D[i = 4*(l>>4) + r][j = l&15]
 //
 // Files: this one holds the token-resident whole-step kernel k_stack (large batches), the A/B kernels, the small
-// kernels and every C-ABI entry point; syn_latency.inc the persistent small-batch kernel k_lat; syn_wavenc.inc the
+// kernels and the C-ABI entry points of the step, the packs, the layout converters and syn_linear* (an entry point is
+// defined once, in the file that holds the kernels it launches: every other one sits at the end of its .inc); syn_latency.inc the persistent small-batch kernel k_lat; syn_wavenc.inc the
 // WavEncoder convolutions (per-clip conditioning); syn_train.inc the fp32 forward / backward kernels of the
 // training path; syn_step_plan.inc (plain C++, no HIP) the choice of the kernel that runs a step.
 #include <hip/hip_runtime.h>
@@ -1652,7 +1653,29 @@ static int g_gemm_resident = 2;      // 16-row plain GEMMs: 2 = 16 x 128 tiles, 
 #include "syn_step_plan.inc"
 static_assert(kPlanT == SYN_T && kPlanXcds == lat::kGroups, "the step planner restates the sequence length and the XCD count");
 
-int device_cus();
+int device_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipGetDevice(&dev);
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
+// k_lat is written for 8 XCDs x 32 CUs (MI355X in SPX mode): one workgroup per CU, all co-resident.
+bool latency_path_ok() {
+    static int ok = -1;
+    if (ok < 0) {
+        int dev = 0, cus = 0;
+        hipGetDevice(&dev);
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        ok = cus == lat::kGroups * lat::kP ? 1 : 0;
+    }
+    return ok == 1;
+}
+
 constexpr int kN128Lds = 128 * 1024;
 // Row tile of the 128-column plain GEMM: the largest of 64 / 32 / 16 that still gives every CU a workgroup (fewer bytes through each CU's L1
 // port: a workgroup pulls (MT + 128) x K x 2) and whose activation block fits the LDS; 0 = the shape does not fit this kernel at all.
@@ -1757,11 +1780,17 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
     return launched("k_stack launch");
 }
 
+}  // namespace
+
+// One subsystem per file, included at global scope: each puts its kernels and helpers into (anonymous)::<its namespace> - the unnamed namespace
+// above, reopened - and defines its C-ABI entry points behind them, at global scope (inside the unnamed namespace an extern "C" function would
+// have internal linkage and not be exported).  syn_conv_train.inc is host code only: the training convolutions' launches over wav:: kernels.
 #include "syn_stack_train.inc"
 #include "syn_seq.inc"
 #include "syn_cond.inc"
 #include "syn_wavenc.inc"
 #include "syn_train.inc"
+#include "syn_conv_train.inc"
 #include "syn_glue.inc"
 #include "syn_rvq.inc"
 #include "syn_rvq_train.inc"
@@ -1776,108 +1805,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_joints.inc"
 #include "syn_mesh.inc"
 
-// ---- WavEncoder forward: lengths, workspace layout and the 12 launches ----------------------------------------
-struct WavPlan {
-    int L1, L2, L3, L4;                 // positions after blocks 0, 1(=2), 3(=4), 5
-    long z0, s0, x1, z1, s1, x2, z2, x3, z3, s3, x4, z4, x5, z5, s5, per_clip;   // element (bf16) offsets inside a clip's workspace
-};
-constexpr int kHalo = 7, kSlack = 16;   // zero rows in front of / behind padded tensors; zero tail rows of the grouped ones
-WavPlan wav_plan(int L) {
-    WavPlan p;
-    p.L1 = (L + 2 * 1700 - 15) / 5 + 1;
-    p.L2 = (p.L1 - 15) / 6 + 1;
-    p.L3 = (p.L2 - 15) / 6 + 1;
-    p.L4 = (p.L3 - 15) / 3 + 1;
-    long o = 0;
-    auto take = [&](long rows, int ch) { const long at = o; o += rows * ch; o = (o + 63) & ~63L; return at; };
-    const long h2 = p.L2 + 2 * kHalo + kSlack, h3 = p.L3 + 2 * kHalo + kSlack, h4 = p.L4 + 2 * kHalo + kSlack;
-    p.z0 = p.s0 = 0;      /* block 0's intermediates never leave the chip (k_block0) */  p.x1 = take(p.L1 + kSlack, 64);
-    p.z1 = take(h2, 64);  p.s1 = take(p.L2, 64);  p.x2 = take(h2, 64);
-    p.z2 = take(h2, 64);  p.x3 = take(p.L2 + kSlack, 64);
-    p.z3 = take(h3, 128); p.s3 = take(p.L3, 128); p.x4 = take(h3, 128);
-    p.z4 = take(h3, 128); p.x5 = take(p.L3 + kSlack, 128);
-    p.z5 = take(h4, 256); p.s5 = take(p.L4, 256);
-    p.per_clip = o;
-    return p;
-}
-
-template <int CINP, int KT, int WN, int WM, int RF, int EPI>
-int launch_conv(const wav::CArgs& a, int n_clips, hipStream_t s) {
-    constexpr int MW = WM * RF * 16, lds = (MW + KT - 1) * (CINP * 2 + 16);
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(wav::k_conv<CINP, KT, WN, WM, RF, EPI>, lds); }
-    hipLaunchKernelGGL((wav::k_conv<CINP, KT, WN, WM, RF, EPI>), dim3((a.L_out + MW - 1) / MW, n_clips), dim3(WN * WM * 64), lds, s, a);
-    return launched("k_conv launch");
-}
-
-// diagnostics (syn_debug_conv_terms): which of the two cross products of the split-operand convolutions are issued (3 = both)
-// Default (-1): forward and data gradient issue both cross products (fp32-grade: the forward activations feed batch statistics, and rounding them to bf16
-// moved the first blocks' gradients by 14 %); the WEIGHT gradient drops the dy_hi . x_lo product, i.e. reads x rounded to bf16 - a sum over
-// 10^4 - 10^5 positions per element averages that rounding out (r4 A/B, profiles/r04_ab_conv_terms.txt: every gradient within the same error as with
-// the third product, -0.08 ms per step).
-static int g_conv_terms = -1;
-static inline int conv_terms(bool wgrad) { return g_conv_terms >= 0 ? g_conv_terms : (wgrad ? 1 : 3); }
-
-template <int CINP, int KT, int RF>
-int launch_conv_train_ks(const wav::TArgs& a0, int n_clips, hipStream_t s) {
-    wav::TArgs a = a0; a.terms = conv_terms(false); a.dbg = nullptr;
-    constexpr int MW = RF * 16, lds = 2 * (MW + KT - 1) * (CINP * 2 + wav::kTrainPad);
-    static_assert(lds <= 160 * 1024, "two bf16 planes of the input tile must fit the LDS");
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(wav::k_conv_train_ks<CINP, KT, RF>, lds); }
-    hipLaunchKernelGGL((wav::k_conv_train_ks<CINP, KT, RF>), dim3((a.L_out + MW - 1) / MW, n_clips), dim3(256), lds, s, a);
-    return launched("k_conv_train_ks launch");
-}
-
-// n_out: output channels this launch covers (a multiple of the instance's WN x NF x 16 channels per workgroup: grid z)
-template <int CINP, int KT, int WN, int WM, int RF, int NF = 4, bool DUAL = false>
-int launch_conv_train(const wav::TArgs& a0, int n_clips, hipStream_t s, int n_out = WN * NF * 16) {
-    wav::TArgs a = a0; a.terms = conv_terms(false); a.dbg = g_dbg_attn;
-    constexpr int MW = WM * RF * 16, lds = 2 * (MW + KT - 1) * (CINP * 2 + wav::kTrainPad), NT = WN * NF * 16;
-    static_assert(lds <= 160 * 1024, "two bf16 planes of the input tile must fit the LDS");
-    if (n_out % NT) return fail_msg("k_conv_train: the launch's channels are not a multiple of the instance's channel block");
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(wav::k_conv_train<CINP, KT, WN, WM, RF, NF, DUAL>, lds); }
-    hipLaunchKernelGGL((wav::k_conv_train<CINP, KT, WN, WM, RF, NF, DUAL>), dim3((a.L_out + MW - 1) / MW, n_clips, n_out / NT), dim3(WN * WM * 64), lds, s, a);
-    return launched("k_conv_train launch");
-}
-
-template <int CO_T, int TAPS, bool DUAL = false>
-int launch_wgrad_s(const wav::WArgs& a0, hipStream_t s) {
-    wav::WArgs a = a0; a.terms = conv_terms(true); a.dbg = g_dbg_attn;
-    static_assert(wav::wgrad_s_lds(CO_T) <= 160 * 1024, "dy and x' tiles must fit the LDS");
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(wav::k_conv_wgrad_s<CO_T, TAPS, DUAL>, wav::wgrad_s_lds(CO_T)); }
-    hipLaunchKernelGGL((wav::k_conv_wgrad_s<CO_T, TAPS, DUAL>), dim3(a.cin / wav::kWsJ, a.shares, DUAL ? 1 : a.co_n / CO_T), dim3(512), wav::wgrad_s_lds(CO_T), s, a);
-    return launched("k_conv_wgrad_s launch");
-}
-
-// The 128- / 256-channel stride-1 layers on 64-channel output tiles (grid z) with 32 input channels per workgroup: the gradient is cut in cout / 64 x cin / 32 slices
-// (8 / 32) instead of cin / 32 (4) or cin / 16 (16), so the same number of workgroups needs that many fewer position shares - and every share is a full-size partial
-// gradient written here and read back by syn_conv1d_wgrad_sums (r6: 87 MB -> 22 MB per 128-channel layer, 126 -> 31 MB for the 256-channel one; the three launches
-// 104 + 49 -> 120 us, the sums 159 -> 137 us per step; 16 input channels per workgroup measured 134 us - the dy fragments are then re-read from the LDS per 24 MFMAs)
-constexpr int kWgradWideCb = 2;
-// The short 64-channel layers (blocks 1 - 2: 18 chunks per clip) likewise on two slices of 32 input channels (186 -> 93 shares of 245 KB: the three launches 134 -> 103 us);
-// block 0's conv2 (105 chunks per clip, dy = 117 MB) stays on one slice: staging its dy tiles twice costs what the smaller partial sums save (166 -> 174 us)
-static bool wgrad64_two_slices(int l_out) { return (l_out + wav::kWgP - 1) / wav::kWgP < 50; }
-template <int CO_T, int TAPS, int CB>
-int launch_wgrad_tiled(const wav::WArgs& a0, hipStream_t s) {
-    wav::WArgs a = a0; a.terms = conv_terms(true); a.dbg = g_dbg_attn;
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(wav::k_conv_wgrad<CO_T, TAPS, CB>, wav::wgrad_lds2(CO_T, CB)); }
-    hipLaunchKernelGGL((wav::k_conv_wgrad<CO_T, TAPS, CB>), dim3(a.cin / (16 * CB), a.shares, a.co_n / CO_T), dim3(512), wav::wgrad_lds2(CO_T, CB), s, a);
-    return launched("k_conv_wgrad (tiled) launch");
-}
-
-template <int CO, int TAPS>
-int launch_wgrad(const wav::WArgs& a0, hipStream_t s) {
-    wav::WArgs a = a0; a.terms = conv_terms(true); a.dbg = g_dbg_attn;
-    static OncePerDevice once;
-    constexpr int CB = wav::wgrad_cb(CO);
-    if (once.first()) { allow_lds(wav::k_conv_wgrad<CO, TAPS, CB>, wav::wgrad_lds(CO)); }
-    hipLaunchKernelGGL((wav::k_conv_wgrad<CO, TAPS, CB>), dim3(a.cin / (16 * CB), a.shares), dim3(512), wav::wgrad_lds(CO), s, a);
-    return launched("k_conv_wgrad launch");
-}
+namespace {
 
 int launch_latency(const lat::LArgs& a, hipStream_t s) {
     static OncePerDevice once;
@@ -1902,29 +1830,6 @@ int launch_seq(const seq::QArgs& a, hipStream_t s) {
         if (nz == 2) launch_seq_as<true, 2>(a, grid, s); else if (nz == 1) launch_seq_as<true, 1>(a, grid, s); else launch_seq_as<true, 0>(a, grid, s);
     }
     return launched("k_seq launch");
-}
-
-int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
-// k_lat is written for 8 XCDs x 32 CUs (MI355X in SPX mode): one workgroup per CU, all co-resident.
-bool latency_path_ok() {
-    static int ok = -1;
-    if (ok < 0) {
-        int dev = 0, cus = 0;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        ok = cus == lat::kGroups * lat::kP ? 1 : 0;
-    }
-    return ok == 1;
 }
 
 }  // namespace
@@ -2001,261 +1906,6 @@ int syn_axpby_rows(const float* x, const float* y, const float* coef_ab, const i
     return launched("k_axpby_rows launch");
 }
 
-// ---- RVQ-VAE (syn_rvq.inc) ----------------------------------------------------------------------------------------
-int syn_vq_conv1d(const syn_vq_conv* cv, const void* x_bf16, const float* resid, float* y_f32, int32_t ldy, void* y_bf16,
-                  int32_t clips, int32_t t_in, int32_t t_out, void* stream) {
-    if (!cv || !cv->w_packed || !cv->bias || !x_bf16 || (!y_f32 && !y_bf16) || clips <= 0 || t_in <= 0 || t_out <= 0)
-        return fail_msg("syn_vq_conv1d: bad arguments");
-    if (cv->cin % 32 || cv->cout % 128 || cv->taps < 1 || cv->stride < 1 || cv->dil < 1 || cv->up < 0 || cv->up > 1)
-        return fail_msg("syn_vq_conv1d: cin must be a multiple of 32, cout of 128, up 0 or 1");
-    rvq::CvArgs a;
-    a.X = (const __bf16*)x_bf16; a.W = (const uint4*)cv->w_packed; a.bias = cv->bias; a.R = resid; a.Yf = y_f32; a.Yb = (__bf16*)y_bf16;
-    a.t_in = t_in; a.t_out = t_out; a.cin = cv->cin; a.cout = cv->cout; a.cout_valid = cv->cout_valid; a.ldy = ldy;
-    a.taps = cv->taps; a.stride = cv->stride; a.dil = cv->dil; a.pad = cv->pad; a.up = cv->up; a.relu_in = cv->relu_in; a.relu_out = cv->relu_out;
-    // 32 output positions per workgroup: its window (34-66 rows, <= 69 KB) lets 2-4 workgroups share a CU; 64-position
-    // tiles (one workgroup per CU, half the weight re-reads) measured 5 % slower at 256 clips
-    constexpr int mf = 2, mt = mf * 16;
-    const int rows = (((mt - 1) * cv->stride + (cv->taps - 1) * cv->dil) >> cv->up) + 2;
-    const int lds = rows * (cv->cin * 2 + 16);
-    if (lds > 160 * 1024) return fail_msg("syn_vq_conv1d: input window does not fit LDS");
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(rvq::k_conv1d<2>, 160 * 1024); }
-    const dim3 grid((t_out + mt - 1) / mt, cv->cout / 128, clips);
-    hipLaunchKernelGGL(rvq::k_conv1d<mf>, grid, dim3(rvq::kCvThreads), lds, (hipStream_t)stream, a);
-    return launched("k_conv1d launch");
-}
-
-namespace {
-int vq_conv(const syn_vq_conv& base, int up, int relu_in, int relu_out, const void* x, const float* resid, float* yf, int ldy, void* yb,
-            int clips, int t_in, int t_out, void* stream) {
-    syn_vq_conv cv = base;
-    cv.up = up; cv.relu_in = relu_in; cv.relu_out = relu_out;
-    return syn_vq_conv1d(&cv, x, resid, yf, ldy, yb, clips, t_in, t_out, stream);
-}
-
-struct VqWs { float* af; __bf16* ab; float* bf; __bf16* bb; __bf16* hb; __bf16* in; };
-VqWs vq_ws(void* ws, int clips, int t_max, int cin_p) {
-    const size_t n = (size_t)clips * t_max * rvq::kDim;
-    char* p = (char*)ws;
-    VqWs w;
-    w.af = (float*)p; p += n * 4;
-    w.bf = (float*)p; p += n * 4;
-    w.ab = (__bf16*)p; p += n * 2;
-    w.bb = (__bf16*)p; p += n * 2;
-    w.hb = (__bf16*)p; p += n * 2;
-    w.in = (__bf16*)p;
-    (void)cin_p;
-    return w;
-}
-
-// Resnet1D (models/vq/resnet.py:71-83): 3 x { x += conv2(relu(conv1(relu(x)))) }, dilations 9, 3, 1, on (af, ab) in place
-int vq_resnet(const syn_vq_conv* c, VqWs& w, int clips, int t, void* stream) {
-    for (int j = 0; j < 3; ++j) {
-        int rc = vq_conv(c[2 * j], 0, 1, 0, w.ab, nullptr, nullptr, 0, w.hb, clips, t, t, stream);
-        if (rc) return rc;
-        if ((rc = vq_conv(c[2 * j + 1], 0, 1, 0, w.hb, w.af, w.af, rvq::kDim, w.ab, clips, t, t, stream))) return rc;
-    }
-    return 0;
-}
-
-__global__ void k_vq_pose_in(const float* pose, __bf16* out, long rows, int d, int dp) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * dp) return;
-    const long r = i / dp; const int c = (int)(i - r * dp);
-    out[i] = c < d ? (__bf16)pose[r * d + c] : (__bf16)0.f;
-}
-}  // namespace
-
-int64_t syn_vq_workspace_bytes(int32_t clips, int32_t t_pose, int32_t pose_dim) {
-    if (clips <= 0 || t_pose <= 0 || pose_dim <= 0) return -1;
-    const int64_t n = (int64_t)clips * t_pose * rvq::kDim;
-    const int64_t in_row = ((pose_dim + 31) / 32 * 32) * 2;            // padded bf16 pose row; also holds the quantised rows (256 B per pose frame)
-    return n * 14 + (int64_t)clips * t_pose * (in_row > 256 ? in_row : 256) + 256;
-}
-
-int syn_vq_map2latent(const syn_vq_model* m, const float* pose, int32_t clips, int32_t t_pose, void* workspace, float* latent,
-                      void* stream) {
-    if (!m || !pose || !workspace || !latent || clips <= 0 || t_pose <= 0 || t_pose % 4) return fail_msg("syn_vq_map2latent: bad arguments (frames % 4 == 0)");
-    const int dp = m->enc[0].cin;
-    VqWs w = vq_ws(workspace, clips, t_pose, dp);
-    const long rows = (long)clips * t_pose;
-    hipLaunchKernelGGL(k_vq_pose_in, dim3((unsigned)((rows * dp + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pose, w.in, rows, m->pose_dim, dp);
-    int rc, t = t_pose;
-    if ((rc = vq_conv(m->enc[0], 0, 0, 1, w.in, nullptr, w.af, rvq::kDim, w.ab, clips, t, t, stream))) return rc;     // conv + ReLU (encdec.py:23-24)
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = vq_conv(m->enc[1 + 7 * i], 0, 0, 0, w.ab, nullptr, w.bf, rvq::kDim, w.bb, clips, t, t / 2, stream))) return rc;   // k4 s2 (:27-29)
-        t /= 2;
-        { float* f = w.af; w.af = w.bf; w.bf = f; __bf16* b = w.ab; w.ab = w.bb; w.bb = b; }
-        if ((rc = vq_resnet(m->enc + 2 + 7 * i, w, clips, t, stream))) return rc;
-    }
-    return vq_conv(m->enc[15], 0, 0, 0, w.ab, nullptr, latent, rvq::kDim, nullptr, clips, t, t, stream);           // (:33)
-}
-
-namespace {
-int vq_decode(const syn_vq_model* m, VqWs& w, const __bf16* qb, int clips, int t, float* pose_out, void* stream) {
-    int rc;
-    if ((rc = vq_conv(m->dec[0], 0, 0, 1, qb, nullptr, w.af, rvq::kDim, w.ab, clips, t, t, stream))) return rc;        // conv + ReLU (encdec.py:50-51)
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = vq_resnet(m->dec + 1 + 7 * i, w, clips, t, stream))) return rc;
-        if ((rc = vq_conv(m->dec[7 + 7 * i], 1, 0, 0, w.ab, nullptr, w.bf, rvq::kDim, w.bb, clips, t, 2 * t, stream))) return rc;   // Upsample x2 + conv (:55-57)
-        t *= 2;
-        { float* f = w.af; w.af = w.bf; w.bf = f; __bf16* b = w.ab; w.ab = w.bb; w.bb = b; }
-    }
-    if ((rc = vq_conv(m->dec[15], 0, 0, 1, w.ab, nullptr, nullptr, 0, w.hb, clips, t, t, stream))) return rc;          // conv + ReLU (:60-61)
-    return vq_conv(m->dec[16], 0, 0, 0, w.hb, nullptr, pose_out, m->pose_dim, nullptr, clips, t, t, stream);          // (:62), (N, T, D)
-}
-}  // namespace
-
-int syn_vq_latent2origin(const syn_vq_model* m, const float* latent, int32_t clips, int32_t t_lat, void* workspace, float* pose_out,
-                         int32_t* idx, float* sqerr, int32_t* hist, void* stream) {
-    if (!m || !latent || !workspace || !pose_out || !idx || !sqerr || !hist || clips <= 0 || t_lat <= 0) return fail_msg("syn_vq_latent2origin: bad arguments");
-    VqWs w = vq_ws(workspace, clips, 4 * t_lat, m->enc[0].cin);
-    // quantised rows: fp32 into bf (free until the first up-conv), bf16 into the input region (the decoder's operand)
-    int rc = syn_vq_quantize(latent, m->codebooks, m->codebooks_t, m->code_sq, w.bf, w.in, idx, sqerr, hist, clips * t_lat, stream);
-    if (rc) return rc;
-    return vq_decode(m, w, w.in, clips, t_lat, pose_out, stream);
-}
-
-int syn_vq_forward_decoder(const syn_vq_model* m, const int32_t* idx, int32_t n_q, int32_t clips, int32_t t_lat, void* workspace,
-                           float* pose_out, void* stream) {
-    if (!m || !idx || !workspace || !pose_out || clips <= 0 || t_lat <= 0) return fail_msg("syn_vq_forward_decoder: bad arguments");
-    VqWs w = vq_ws(workspace, clips, 4 * t_lat, m->enc[0].cin);
-    int rc = syn_vq_codes(idx, m->codebooks, w.bf, w.in, clips * t_lat, n_q, stream);
-    if (rc) return rc;
-    return vq_decode(m, w, w.in, clips, t_lat, pose_out, stream);
-}
-
-int32_t syn_vq_quantize_groups(int32_t rows) { return (rows + rvq::q_rows(rows) - 1) / rvq::q_rows(rows); }
-
-int syn_vq_quantize(const float* x, const float* codebooks, const float* codebooks_t, const float* code_sq, float* q_f32,
-                    void* q_bf16, int32_t* idx, float* sqerr, int32_t* hist, int32_t rows, void* stream) {
-    if (!x || !codebooks || !codebooks_t || !code_sq || !q_f32 || !idx || !sqerr || !hist || rows <= 0)
-        return fail_msg("syn_vq_quantize: bad arguments");
-    rvq::QArgs a;
-    a.X = x; a.CB = codebooks; a.CBT = codebooks_t; a.CC = code_sq; a.Qf = q_f32; a.Qb = (__bf16*)q_bf16; a.idx = idx;
-    a.sqerr = sqerr; a.hist = hist; a.rows = rows;
-    if (rvq::q_rows(rows) == 4) hipLaunchKernelGGL(rvq::k_quantize<4>, dim3(syn_vq_quantize_groups(rows)), dim3(rvq::kQThreads), 0, (hipStream_t)stream, a);
-    else                        hipLaunchKernelGGL(rvq::k_quantize<16>, dim3(syn_vq_quantize_groups(rows)), dim3(rvq::kQThreads), 0, (hipStream_t)stream, a);
-    return launched("k_quantize launch");
-}
-
-int syn_vq_codes(const int32_t* idx, const float* codebooks, float* q_f32, void* q_bf16, int32_t rows, int32_t n_q, void* stream) {
-    if (!idx || !codebooks || !q_f32 || rows <= 0 || n_q < 1 || n_q > rvq::kQ) return fail_msg("syn_vq_codes: bad arguments");
-    hipLaunchKernelGGL(rvq::k_codes, dim3(rows), dim3(rvq::kDim), 0, (hipStream_t)stream, idx, codebooks, q_f32, (__bf16*)q_bf16, rows, n_q);
-    return launched("k_codes launch");
-}
-
-// ---- RVQ-VAE training (syn_rvq_train.inc) ------------------------------------------------------------------------------------------
-int syn_vq_train_pack(const void* jobs_dev, int32_t n_jobs, int32_t max_units, void* stream) {
-    if (!jobs_dev || n_jobs <= 0 || max_units <= 0) return fail_msg("syn_vq_train_pack: bad arguments");
-    hipLaunchKernelGGL(rvqt::k_pack_jobs, dim3((max_units + 255) / 256, n_jobs), dim3(256), 0, (hipStream_t)stream, (const rvqt::PackJob*)jobs_dev);
-    return launched("k_pack_jobs launch");
-}
-
-int syn_vq_train_cast(const float* x, int64_t rows, int32_t dim, int32_t dim_padded, void* out_bf16, void* out_lo_bf16, void* stream) {
-    if (!x || !out_bf16 || rows <= 0 || dim <= 0 || dim_padded < dim) return fail_msg("syn_vq_train_cast: bad arguments");
-    const long n = (long)rows * dim_padded;
-    hipLaunchKernelGGL(rvqt::k_cast_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (__bf16*)out_bf16, (__bf16*)out_lo_bf16, n, dim, dim_padded);
-    return launched("k_cast_pad launch");
-}
-
-int syn_vq_train_ew(const float* v, const float* resid, const void* relu_src_bf16, const uint8_t* keep, float scale_v, float scale_resid,
-                    float* out_f32, void* out_bf16, void* out_lo_bf16, int32_t lo_relu, int64_t n, void* stream) {
-    if (!v || (!out_f32 && !out_bf16 && !out_lo_bf16) || n <= 0 || n % 4) return fail_msg("syn_vq_train_ew: bad arguments (n % 4 == 0)");
-    hipLaunchKernelGGL(rvqt::k_ew, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, resid, (const __bf16*)relu_src_bf16, keep,
-                       scale_v, scale_resid, out_f32, (__bf16*)out_bf16, (__bf16*)out_lo_bf16, lo_relu, (long)(n / 4));
-    return launched("k_ew launch");
-}
-
-int syn_vq_train_pairsum(const float* du, float* out, int64_t rows_out, int32_t channels, void* stream) {
-    if (!du || !out || rows_out <= 0 || channels <= 0 || channels % 4) return fail_msg("syn_vq_train_pairsum: bad arguments (channels % 4 == 0)");
-    const long n4 = (long)rows_out * (channels / 4);
-    hipLaunchKernelGGL(rvqt::k_pairsum, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, du, out, n4, channels / 4);
-    return launched("k_pairsum launch");
-}
-
-int syn_vq_train_stuff(const void* dy_bf16, void* out_bf16, int64_t rows_in, int32_t channels, void* stream) {
-    if (!dy_bf16 || !out_bf16 || rows_in <= 0 || channels <= 0 || channels % 8) return fail_msg("syn_vq_train_stuff: bad arguments (channels % 8 == 0)");
-    const long n8 = (long)rows_in * (channels / 8);
-    hipLaunchKernelGGL(rvqt::k_stuff, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)dy_bf16, (uint4*)out_bf16, n8, channels / 8);
-    return launched("k_stuff launch");
-}
-
-int syn_vq_train_wgrad(const void* dy_bf16, int32_t ldy, const void* x_bf16, int32_t ldx, float* dw, float* db, int32_t clips, int32_t t_in,
-                       int32_t t_out, int32_t cout, int32_t cin, int32_t taps, int32_t stride, int32_t dil, int32_t pad, int32_t up, int32_t relu_in,
-                       void* stream) {
-    if (!dy_bf16 || !x_bf16 || !dw || clips <= 0 || t_in <= 0 || t_out <= 0 || cout <= 0 || cin <= 0 || taps <= 0 || stride <= 0 || dil <= 0 || pad < 0 ||
-        up < 0 || up > 1 || ldy < cout || ldx < cin || ldy % 8 || ldx % 8 || (int64_t)clips * t_out >= (1ll << 30) || (int64_t)clips * t_in >= (1ll << 30))
-        return fail_msg("syn_vq_train_wgrad: bad arguments (row pitches: multiples of 8 channels that hold cout / cin)");
-    rvqt::WgArgs a;
-    a.DY = (const __bf16*)dy_bf16; a.X = (const __bf16*)x_bf16; a.dW = dw; a.ldy = ldy; a.ldx = ldx; a.clips = clips; a.t_in = t_in; a.t_out = t_out;
-    a.cout = cout; a.cin = cin; a.taps = taps; a.stride = stride; a.dil = dil; a.pad = pad; a.up = up; a.relu_in = relu_in;
-    hipLaunchKernelGGL(rvqt::k_wgrad, dim3((cout + 63) / 64, (cin + 63) / 64, taps), dim3(256), 0, (hipStream_t)stream, a);
-    int rc = launched("k_wgrad launch");
-    if (rc || !db) return rc;
-    hipLaunchKernelGGL(rvqt::k_colsum, dim3((cout + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const __bf16*)dy_bf16, ldy, clips * t_out, cout, db);
-    return launched("k_colsum launch");
-}
-
-int syn_vq_train_codebook_prep(const float* codebook, float* codebook_t, float* code_sq, void* stream) {
-    if (!codebook || !codebook_t || !code_sq) return fail_msg("syn_vq_train_codebook_prep: bad arguments");
-    hipLaunchKernelGGL(rvqt::k_cb_t, dim3(rvq::kCodes / 32, rvq::kDim / 32), dim3(256), 0, (hipStream_t)stream, codebook, codebook_t);
-    hipLaunchKernelGGL(rvqt::k_cb_sq, dim3(rvq::kCodes / 256), dim3(256), 0, (hipStream_t)stream, (const float*)codebook_t, code_sq);
-    return launched("k_cb_t / k_cb_sq launch");
-}
-
-int syn_vq_train_tile(const float* x, int32_t rows, const float* noise, float* codebook, float* code_sum, float* code_count, void* stream) {
-    if (!x || rows <= 0 || (rows < rvq::kCodes && !noise) || !codebook || !code_sum || !code_count) return fail_msg("syn_vq_train_tile: bad arguments (fewer rows than codes need the noise)");
-    hipLaunchKernelGGL(rvqt::k_tile_init, dim3(rvq::kCodes), dim3(256), 0, (hipStream_t)stream, x, rows, noise, (float)(0.01 / sqrt((double)rvq::kDim)), codebook, code_sum, code_count);
-    return launched("k_tile_init launch");
-}
-
-int syn_vq_train_quantize(const float* x_in, const float* codebook, const float* codebook_t, const float* code_sq, const float* gumbel, float temperature,
-                          float* x_out, float* q_acc, void* q_bf16, float* resid_sum, int32_t* idx, float* sqerr, int32_t layer, int32_t first, int32_t rows,
-                          void* stream) {
-    if (!x_in || !codebook || !codebook_t || !code_sq || !x_out || x_out == x_in || !q_acc || !resid_sum || !idx || !sqerr || layer < 0 || layer >= rvq::kQ ||
-        rows <= 0 || (gumbel && !(temperature > 0.f)))
-        return fail_msg("syn_vq_train_quantize: bad arguments");
-    rvqt::QtArgs a;
-    a.Xin = x_in; a.CB = codebook; a.CBT = codebook_t; a.CC = code_sq; a.G = gumbel; a.temperature = temperature; a.Xout = x_out; a.Qacc = q_acc;
-    a.Qb = (__bf16*)q_bf16; a.Rsum = resid_sum; a.idx = idx; a.sqerr = sqerr; a.layer = layer; a.first = first; a.rows = rows;
-    const int groups = syn_vq_quantize_groups(rows);
-    if (rvq::q_rows(rows) == 4) hipLaunchKernelGGL(rvqt::k_quantize_train<4>, dim3(groups), dim3(256), 0, (hipStream_t)stream, a);
-    else                        hipLaunchKernelGGL(rvqt::k_quantize_train<16>, dim3(groups), dim3(256), 0, (hipStream_t)stream, a);
-    return launched("k_quantize_train launch");
-}
-
-int syn_vq_train_codebook_update(const float* x_in, const int32_t* idx, int32_t layer, int32_t rows, const float* noise, float mu, float one_minus_mu,
-                                 float* codebook, float* code_sum, float* code_count, float* batch_count, void* stream) {
-    if (!x_in || !idx || layer < 0 || layer >= rvq::kQ || rows <= 0 || (rows < rvq::kCodes && !noise) || !codebook || !code_sum || !code_count || !batch_count)
-        return fail_msg("syn_vq_train_codebook_update: bad arguments (fewer rows than codes need the noise)");
-    hipLaunchKernelGGL(rvqt::k_code_update, dim3(rvq::kCodes), dim3(256), 0, (hipStream_t)stream, x_in, idx, layer, rows, noise,
-                       (float)(0.01 / sqrt((double)rvq::kDim)), mu, one_minus_mu, codebook, code_sum, code_count, batch_count);
-    return launched("k_code_update launch");
-}
-
-int32_t syn_vq_train_loss_parts(int64_t rows, int32_t dim_padded) {
-    if (rows <= 0 || dim_padded <= 0) return -1;
-    return (int32_t)((rows * dim_padded + 256 * rvqt::kLossPer - 1) / (256 * rvqt::kLossPer));
-}
-
-int syn_vq_train_loss(const float* rec, const float* gt, int64_t rows, int32_t dim, int32_t dim_padded, int32_t kind, void* d_rec_bf16, float* parts,
-                      void* stream) {
-    if (!rec || !gt || !d_rec_bf16 || !parts || rows <= 0 || dim <= 0 || dim_padded < dim || kind < 0 || kind > 2) return fail_msg("syn_vq_train_loss: bad arguments");
-    hipLaunchKernelGGL(rvqt::k_recons, dim3(syn_vq_train_loss_parts(rows, dim_padded)), dim3(256), 0, (hipStream_t)stream, rec, gt, (long)rows * dim_padded, dim,
-                       dim_padded, kind, (float)(1.0 / ((double)rows * dim)), (__bf16*)d_rec_bf16, parts);
-    return launched("k_recons launch");
-}
-
-int syn_vq_train_scalars(const float* parts, int32_t n_parts, int64_t count, const float* sqerr, int32_t groups, const float* batch_count, int32_t n_active,
-                         int32_t rows, float commit_weight, float* out4, void* stream) {
-    if (!parts || n_parts <= 0 || count <= 0 || !sqerr || groups <= 0 || !batch_count || n_active < 1 || n_active > rvq::kQ || rows <= 0 || !out4)
-        return fail_msg("syn_vq_train_scalars: bad arguments");
-    hipLaunchKernelGGL(rvqt::k_scalars, dim3(1), dim3(512), 0, (hipStream_t)stream, parts, n_parts, (float)(1.0 / (double)count), sqerr, groups, batch_count,
-                       n_active, rows, commit_weight, out4);
-    return launched("k_scalars launch");
-}
-
 int syn_steps_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, int32_t n_t_model, int32_t* t_coef, int32_t n_t_coef,
                       int32_t n_steps, void* stream) {
     if (!sched || !counter || !t_model || !t_coef || n_t_model <= 0 || n_t_coef <= 0 || n_steps <= 0)
@@ -2270,148 +1920,12 @@ int syn_step_advance(const int32_t* sched, int32_t* counter, int32_t* t_model, i
     return syn_steps_advance(sched, counter, t_model, n_t_model, t_coef, n_t_coef, 1, stream);
 }
 
-int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
-                    float* ring, float* h, int64_t n, void* stream) {
-    return plms::update(table, n_rows, counter, back, x_t, pred_x0, ring, h, n, stream);
-}
-
-int syn_bpd_terms(const syn_bpd_row* table, int32_t n_rows, const int32_t* t_row, const int32_t* clip, const float* x_start, int32_t n_clips,
-                  const float* x_t, const float* noise, const float* pred_x0, int32_t n_seq, float* out, void* stream) {
-    return bpd::terms(table, n_rows, t_row, clip, x_start, n_clips, x_t, noise, pred_x0, n_seq, out, stream);
-}
-
-int syn_guide_in_fwd(const float* x_bct, int32_t n_x, const void* a_packed, const float* cond, const float* te, int32_t n_te, const int32_t* t_model,
-                     const float* rot_cos, const float* rot_sin, int32_t n_live, int32_t n_seq, float* h0, void* stream) {
-    return guide::in_fwd(x_bct, n_x, a_packed, cond, te, n_te, t_model, rot_cos, rot_sin, n_live, n_seq, h0, stream);
-}
-
-int syn_guide_in_bwd(const float* dh0, const void* at_packed, const float* rot_cos, const float* rot_sin, int32_t n_seq, int32_t accumulate, float* dx_bct,
-                     void* stream) {
-    return guide::in_bwd(dh0, at_packed, rot_cos, rot_sin, n_seq, accumulate, dx_bct, stream);
-}
-
-int syn_guide_update(int32_t mode, const float* a, const float* pred_x0, const float* grad, const float* noise, int32_t draw, uint64_t seed,
-                     uint64_t first_clip, const float* coef, int32_t n_rows, const int32_t* t_idx, int32_t n_clips, float* out, void* stream) {
-    return guide::update(mode, a, pred_x0, grad, noise, draw, seed, first_clip, coef, n_rows, t_idx, n_clips, out, stream);
-}
-
-// Motion metrics (syn_joints.inc)
-int syn_fk_joints(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* rot, int32_t rot6d, const float* transl,
-                  const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, const float* pose_mean, float* joints_out, void* stream) {
-    return joints::fk(parents, n_joints, rest_joints, n_takes, rot, rot6d, transl, take_of_frame, frames_per_take, n_frames, pose_mean, joints_out, stream);
-}
-
-int syn_joint_speed(const float* joints_in, int32_t n_takes, int32_t n_frames, int32_t n_joints, float fps, const float* mmae, float* speed, void* stream) {
-    return joints::speed(joints_in, n_takes, n_frames, n_joints, fps, mmae, speed, stream);
-}
-
-int syn_motion_beats(const float* vel, int32_t n_takes, int32_t n_frames, int32_t n_joints, int32_t t_start, int32_t t_end, int32_t order, float threshold,
-                     uint8_t* mask, void* stream) {
-    return joints::beats(vel, n_takes, n_frames, n_joints, t_start, t_end, order, threshold, mask, stream);
-}
-
-int syn_beat_align(const uint8_t* mask, int32_t n_takes, int32_t n_slice, int32_t n_joints, const int32_t* upper_body, int32_t n_upper, const double* onsets,
-                   const int32_t* onset_offsets, double pose_fps, float sigma, float* per_joint, float* bc, void* stream) {
-    return joints::align(mask, n_takes, n_slice, n_joints, upper_body, n_upper, onsets, onset_offsets, pose_fps, sigma, per_joint, bc, stream);
-}
-
-int64_t syn_l1div_workspace_bytes(int32_t n_takes, int64_t n, int32_t channels) { return joints::l1div_workspace(n_takes, n, channels); }
-
-int syn_l1div(const float* x, int32_t n_takes, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
-    return joints::l1div(x, n_takes, n, channels, workspace, blocks, out, stream);
-}
-
-int syn_recover_from_ric(const float* data, int32_t n_seq, int32_t n_frames, int32_t channels, int32_t joints_num, float* joints_out, float* root_quat,
-                         void* stream) {
-    return joints::recover_from_ric(data, n_seq, n_frames, channels, joints_num, joints_out, root_quat, stream);
-}
-
-// SMPL-X mesh (syn_mesh.inc)
-int syn_mesh_pack_dirs(const float* posedirs, const float* exprdirs, int32_t n_verts, int32_t n_pose, int32_t n_expr, float* out, void* stream) {
-    return mesh::pack_dirs(posedirs, exprdirs, n_verts, n_pose, n_expr, out, stream);
-}
-
-int syn_fk_transforms(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* pose, const float* pose_mean,
-                      const float* joint_dirs, const float* expression, int32_t n_expr, int32_t kc, const float* transl, const int32_t* take_of_frame,
-                      int32_t frames_per_take, int64_t n_frames, float* feat, float* xforms, float* joints_out, void* stream) {
-    return mesh::fk_transforms(parents, n_joints, rest_joints, n_takes, pose, pose_mean, joint_dirs, expression, n_expr, kc, transl, take_of_frame,
-                               frames_per_take, n_frames, feat, xforms, joints_out, stream);
-}
-
-int syn_mesh_vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, const float* feat, const float* xforms, int32_t n_joints,
-                      const float* v_shaped, int32_t n_takes, const int32_t* skin_index, const float* skin_weight, int32_t width, const float* transl,
-                      const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* vertices_out, void* stream) {
-    return mesh::vertices(dirs_packed, n_verts, kc, feat, xforms, n_joints, v_shaped, n_takes, skin_index, skin_weight, width, transl, take_of_frame,
-                          frames_per_take, n_frames, vertices_out, stream);
-}
-
-int64_t syn_vertex_losses_workspace_bytes(int64_t n, int32_t channels) { return mesh::losses_workspace(n, channels); }
-
-int syn_vertex_losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
-    return mesh::losses(rec, tar, n, channels, workspace, blocks, out, stream);
-}
-
 int syn_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first_index, void* stream) {
     if (!out || n <= 0 || n % 4 || first_index % 4) return fail_msg("syn_randn: n and first_index must be multiples of 4");
     const long n4 = n / 4;
     hipLaunchKernelGGL(k_randn, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n4, seed,
                        stream_id, (long)(first_index / 4));
     return launched("k_randn launch");
-}
-
-int syn_axis_angle_to_rot6d(const float* axis_angle, int64_t n_joints, float* rot6d, void* stream) {
-    if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_axis_angle_to_rot6d: null pointer / negative count");
-    if (n_joints == 0) return 0;
-    hipLaunchKernelGGL(pose::k_aa_to_rot6d, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, axis_angle, (long)n_joints, rot6d);
-    return launched("k_aa_to_rot6d launch");
-}
-
-int syn_rot6d_to_axis_angle(const float* rot6d, int64_t n_joints, float* axis_angle, void* stream) {
-    if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_rot6d_to_axis_angle: null pointer / negative count");
-    if (n_joints == 0) return 0;
-    hipLaunchKernelGGL(pose::k_rot6d_to_aa, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rot6d, (long)n_joints, axis_angle);
-    return launched("k_rot6d_to_aa launch");
-}
-
-// TMR encoders (syn_tmr.inc)
-int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream) { return tmr::pack_weight(w, n, k, out, stream); }
-
-int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
-                   float* mu, float* logvar, void* stream) {
-    return tmr::encode(m, features, n_seq, max_len, lengths, workspace, mu, logvar, stream);
-}
-
-// DistilBERT in front of the TMR text encoder (syn_bert.inc)
-int syn_bert_encode(const syn_bert_model* m, const int32_t* ids, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
-                    float* hidden, void* stream) {
-    return bert::encode(m, ids, n_seq, max_len, lengths, workspace, hidden, stream);
-}
-
-// FGD motion embedder (syn_skel.inc)
-int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, const float* ms, int32_t cout, int32_t cin, const int32_t* chunk_off,
-                         const int32_t* chunk_k, float* out, void* stream) {
-    return skel::pack_weight(w, mask, ws, ms, cout, cin, chunk_off, chunk_k, out, stream);
-}
-
-int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
-    return skel::encode(m, x, n_clips, n_frames, workspace, out, stream);
-}
-
-// T2M text-motion evaluator (syn_t2m.inc)
-int syn_t2m_pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, int32_t layout, float* out, void* stream) {
-    return t2m::pack_weight(w, n, k, conv_cin, layout, out, stream);
-}
-
-int64_t syn_t2m_workspace_bytes(int32_t n_seq, int32_t max_len, int32_t kind) { return t2m::workspace_bytes(n_seq, max_len, kind); }
-
-int syn_t2m_encode_motion(const syn_t2m_model* m, const float* motions, int32_t n_seq, int32_t n_frames, int32_t ld, const int32_t* lengths_dev,
-                          const int32_t* order_dev, void* workspace, float* out, void* stream) {
-    return t2m::encode_motion(m, motions, n_seq, n_frames, ld, lengths_dev, order_dev, workspace, out, stream);
-}
-
-int syn_t2m_encode_text(const syn_t2m_model* m, const float* word_embs, const float* pos_onehot, int32_t n_seq, int32_t max_len,
-                        const int32_t* lengths_dev, const int32_t* order_dev, void* workspace, float* out, void* stream) {
-    return t2m::encode_text(m, word_embs, pos_onehot, n_seq, max_len, lengths_dev, order_dev, workspace, out, stream);
 }
 
 int syn_test_gemm(const void* x_bf16, const void* w_packed, const float* bias, int32_t m_rows, int32_t n, int32_t k,
@@ -2570,104 +2084,6 @@ int syn_test_handoff(uint32_t* sync_320_zeroed, uint32_t* buf_8x4096, const floa
     return launched("k_handoff_stress launch");
 }
 
-int syn_train_stack_fwd(const syn_train_stack* t, void* stream) {
-    if (!t || !t->h_in || !t->h_out || !t->sync || !t->xch || t->n_seq < 1 || t->n_seq > 64) return fail_msg("syn_train_stack_fwd: 1 .. 64 sequences, non-null pointers");
-    if (!latency_path_ok()) return fail_msg("syn_train_stack_fwd: needs a 256-CU (8 XCD x 32) device");
-    stk::TArgsS a;
-    memset(&a, 0, sizeof(a));
-    a.H = t->h_in; a.Hout = t->h_out; a.dp = t->drop_path; a.M = 32 * t->n_seq; a.tiles = t->n_seq; a.sync = t->sync; a.xch = t->xch; a.flags = t->reserved;
-    for (int l = 0; l < SYN_LAYERS; ++l) {
-        const syn_layer& L = t->layer[l];
-        const syn_train_block_save& S = t->save[l];
-        if (!L.ln1_g || !L.ln1_b || !L.w_qkv || !L.w_proj || !L.b_proj || !L.ln2_g || !L.ln2_b || !L.w_fc1 || !L.b_fc1 || !L.w_fc2 || !L.b_fc2)
-            return fail_msg("syn_train_stack_fwd: a block's weights are incomplete");
-        if (!S.h_attn || !S.mean_attn || !S.rstd_attn || !S.qkv || !S.xt_ln1 || !S.xt_attn || !S.h_mlp || !S.mean_mlp || !S.rstd_mlp || !S.pre || !S.xt_ln2 || !S.xt_gelu)
-            return fail_msg("syn_train_stack_fwd: a block's saved tensors are incomplete");
-        a.layer[l] = L;
-        stk::TrainSave& d = a.save[l];
-        d.hA = S.h_attn; d.meanA = S.mean_attn; d.rstdA = S.rstd_attn; d.qkv = S.qkv; d.xt_ln1 = (uint4*)S.xt_ln1; d.xt_o = (uint4*)S.xt_attn;
-        d.hM = S.h_mlp; d.meanM = S.mean_mlp; d.rstdM = S.rstd_mlp; d.pre = S.pre; d.xt_ln2 = (uint4*)S.xt_ln2; d.xt_a = (uint4*)S.xt_gelu;
-    }
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(stk::k_stack_train, stk::kTrainLds); }
-    const int grid = lat::kGroups * 4 * ((t->n_seq + lat::kGroups - 1) / lat::kGroups);
-    hipLaunchKernelGGL(stk::k_stack_train, dim3(grid), dim3(kThreads), stk::kTrainLds, (hipStream_t)stream, a);
-    return launched("k_stack_train launch");
-}
-
-int syn_train_stack_bwd(const syn_train_stack_grad* t, void* stream) {
-    if (!t || !t->fwd || !t->dh_out || !t->dh_in || !t->stash) return fail_msg("syn_train_stack_bwd: null argument");
-    const syn_train_stack& f = *t->fwd;
-    if (f.n_seq < 1 || f.n_seq > 64 || !f.sync || !f.xch) return fail_msg("syn_train_stack_bwd: 1 .. 64 sequences, the forward's sync / xch");
-    if (!latency_path_ok()) return fail_msg("syn_train_stack_bwd: needs a 256-CU (8 XCD x 32) device");
-    stk::TArgsB a;
-    memset(&a, 0, sizeof(a));
-    a.dH = t->dh_out; a.dHin = t->dh_in; a.dp = f.drop_path; a.M = 32 * f.n_seq; a.tiles = f.n_seq; a.sync = f.sync; a.xch = f.xch; a.stash = t->stash;
-    a.l_first = t->first_block; a.l_last = t->last_block; a.flags = f.reserved;
-    if (a.l_first < a.l_last || a.l_last < 0 || a.l_first >= SYN_LAYERS) return fail_msg("syn_train_stack_bwd: blocks are walked downwards: SYN_LAYERS > first_block >= last_block >= 0");
-    for (int l = 0; l < SYN_LAYERS; ++l) {
-        const syn_layer& L = t->layer_t[l];
-        const syn_train_block_save& S = f.save[l];
-        const syn_train_block_grad& G = t->grad[l];
-        if (!L.ln1_g || !L.w_qkv || !L.w_proj || !L.ln2_g || !L.w_fc1 || !L.w_fc2) return fail_msg("syn_train_stack_bwd: a block's transposed weights / LayerNorm gains are incomplete");
-        if (!G.dyt_fc2 || !G.dyt_fc1 || !G.dyt_proj || !G.dyt_qkv || !G.part) return fail_msg("syn_train_stack_bwd: a block's outputs are incomplete");
-        a.layer[l] = L;
-        stk::TrainSave& d = a.save[l];
-        d.hA = S.h_attn; d.meanA = S.mean_attn; d.rstdA = S.rstd_attn; d.qkv = S.qkv; d.xt_ln1 = (uint4*)S.xt_ln1; d.xt_o = (uint4*)S.xt_attn;
-        d.hM = S.h_mlp; d.meanM = S.mean_mlp; d.rstdM = S.rstd_mlp; d.pre = S.pre; d.xt_ln2 = (uint4*)S.xt_ln2; d.xt_a = (uint4*)S.xt_gelu;
-        stk::TrainGrad& o = a.grad[l];
-        o.dyt_fc2 = (__bf16*)G.dyt_fc2; o.dyt_fc1 = (__bf16*)G.dyt_fc1; o.dyt_proj = (__bf16*)G.dyt_proj; o.dyt_qkv = (__bf16*)G.dyt_qkv; o.part = G.part;
-    }
-    static OncePerDevice once;
-    if (once.first()) { allow_lds(stk::k_stack_train_bwd, stk::kTrainBwdLds); }
-    const int grid = lat::kGroups * 4 * ((f.n_seq + lat::kGroups - 1) / lat::kGroups);
-    hipLaunchKernelGGL(stk::k_stack_train_bwd, dim3(grid), dim3(kThreads), stk::kTrainBwdLds, (hipStream_t)stream, a);
-    return launched("k_stack_train_bwd launch");
-}
-
-// The weight gradients the backward chain left open: per block dW = dY^T . X for its four Linears - dY^T from syn_train_stack_bwd ([features][M] bf16),
-// X^T fragments from the forward - four GEMMs per launch; then the per-sequence partial sums of the bias / LayerNorm gradients added up.
-int syn_train_stack_wgrad(const syn_train_stack_grad* t, void* stream) {
-    if (!t || !t->fwd) return fail_msg("syn_train_stack_wgrad: null argument");
-    const syn_train_stack& f = *t->fwd;
-    const int M = 32 * f.n_seq;
-    if (f.n_seq < 1 || f.n_seq > 64 || M % 128) return fail_msg("syn_train_stack_wgrad: the row count must be a multiple of 128 (4 sequences)");
-    n128_setup();
-    hipStream_t s = (hipStream_t)stream;
-    stk::SmallOut so;
-    memset(&so, 0, sizeof(so));
-    if (t->first_block < t->last_block || t->last_block < 0 || t->first_block >= SYN_LAYERS) return fail_msg("syn_train_stack_wgrad: SYN_LAYERS > first_block >= last_block >= 0");
-    GQuadAll q;
-    memset(&q, 0, sizeof(q));
-    const int ns[4] = {512, 1024, 512, 1536}, ks[4] = {1024, 512, 512, 512};           // dW [n][k]: fc2, fc1, proj, qkv
-    int lds = 0;
-    for (int i = 0; i < 4; ++i) {
-        const int mt = pick_mt128(ns[i], ks[i], M, 8);                // (64-row tiles for all four: 126 us for 8 launches against 182 with proj on 32-row tiles)
-        if (!mt) return fail_msg("syn_train_stack_wgrad: row count too large for the resident GEMM");
-        q.ns[i] = ns[i]; q.ks[i] = ks[i]; q.mt[i] = mt; q.gx[i] = (ns[i] + mt - 1) / mt;
-        q.cum[i + 1] = q.cum[i] + q.gx[i] * (ks[i] / 128);
-        lds = mt * M * 2 > lds ? mt * M * 2 : lds;
-    }
-    q.M = M; q.l0 = t->last_block;
-    for (int l = t->last_block; l <= t->first_block; ++l) {
-        const syn_train_block_save& S = f.save[l];
-        const syn_train_block_grad& G = t->grad[l];
-        if (!G.dw_fc2 || !G.dw_fc1 || !G.dw_proj || !G.dw_qkv || !G.d_ln2_g || !G.d_ln2_b || !G.d_fc2_b || !G.d_fc1_b || !G.d_ln1_g || !G.d_ln1_b || !G.d_proj_b) return fail_msg("syn_train_stack_wgrad: a block's gradient buffers are incomplete");
-        const void* xs[4] = {G.dyt_fc2, G.dyt_fc1, G.dyt_proj, G.dyt_qkv};
-        const void* ws[4] = {S.xt_gelu, S.xt_ln2, S.xt_attn, S.xt_ln1};
-        float* ys[4] = {G.dw_fc2, G.dw_fc1, G.dw_proj, G.dw_qkv};
-        for (int i = 0; i < 4; ++i) { q.X[l][i] = (const __bf16*)xs[i]; q.W[l][i] = (const uint4*)ws[i]; q.Y[l][i] = ys[i]; }
-        // bias / LayerNorm gradients: column sums over the sequences, in sequence order
-        float* const outs[7] = {G.d_ln2_g, G.d_ln2_b, G.d_fc2_b, G.d_fc1_b, G.d_ln1_g, G.d_ln1_b, G.d_proj_b};
-        so.part[l] = G.part;
-        for (int i = 0; i < 7; ++i) so.p[l][i] = outs[i];
-    }
-    // every block's four weight-gradient GEMMs in ONE launch (k_gemm_quad_all)
-    hipLaunchKernelGGL(k_gemm_quad_all, dim3(q.cum[4] * (t->first_block - t->last_block + 1)), dim3(kThreads), lds, s, q);
-    hipLaunchKernelGGL(stk::k_part_sums, dim3((stk::kPartCols + 255) / 256, t->first_block - t->last_block + 1), dim3(256), 0, s, f.n_seq, t->last_block, so);
-    return launched("syn_train_stack_wgrad");
-}
-
 int syn_test_mfma_rate(int32_t iters, float* out, int64_t* flops, void* stream) {
     if (iters <= 0 || !out) return fail_msg("syn_test_mfma_rate: bad arguments (out: 256 floats per CU)");
     static OncePerDevice once;
@@ -2685,842 +2101,11 @@ int syn_test_attention(const void* q, const void* k, const void* vt, int32_t n_s
     return launched("k_attn launch");
 }
 
-// ---- training path: fp32 forward / backward of LayerNorm(512), GELU and the 32-token attention ---------------
-int syn_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* mean, float* rstd, int32_t rows, void* stream) {
-    if (!x || !gamma || !beta || (!y && !y_bf16) || !mean || !rstd || rows <= 0) return fail_msg("syn_ln_fwd: bad arguments");
-    hipLaunchKernelGGL(trn::k_ln_fwd, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, (__bf16*)y_bf16, mean, rstd, rows);
-    return launched("k_ln_fwd launch");
-}
-
-int syn_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
-               float* dgamma, float* dbeta, float* scratch, int32_t rows, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !scratch || rows <= 0) return fail_msg("syn_ln_bwd: bad arguments");
-    const int per = 16, nwg = (rows + per - 1) / per;             // scratch: [nwg][2][512] floats (16 rows per workgroup: 1024 rows = 64 workgroups;
-                                                                  // with 64 rows the 16 workgroups walked their rows one dependent load after the other, 14 us)
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(trn::k_ln_bwd, dim3(nwg), dim3(256), 0, s, dy, x, gamma, mean, rstd, add, dx, scratch, rows, per);
-    hipLaunchKernelGGL(trn::k_colsum, dim3(4), dim3(256), 0, s, scratch, nwg, 2 * SYN_D, SYN_D, dgamma, dbeta);   // partials [p][dgamma | dbeta]
-    return launched("k_ln_bwd launch");
-}
-
-int syn_gelu_fwd(const float* x, float* y, void* y_bf16, int64_t n, void* stream) {
-    if (!x || (!y && !y_bf16) || n <= 0 || n % 4) return fail_msg("syn_gelu_fwd: n must be a positive multiple of 4");
-    hipLaunchKernelGGL(trn::k_gelu_fwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, (__bf16*)y_bf16, (size_t)(n / 4));
-    return launched("k_gelu_fwd launch");
-}
-
-int syn_linear_wgrad_rows(const float* dy, const void* x_bf16, int32_t m_rows, int32_t n, int32_t k, float* dw, float* db, void* stream) {
-    if (!dy || !x_bf16 || !dw || m_rows <= 0 || m_rows > 64 || n <= 0 || n % 16 || k <= 0)
-        return fail_msg("syn_linear_wgrad_rows: 1 .. 64 rows, n a multiple of 16");
-    hipLaunchKernelGGL(trn::k_linear_wgrad_rows, dim3((k + 255) / 256, n / 16), dim3(256), 0, (hipStream_t)stream, dy, (const __bf16*)x_bf16, m_rows, n, k, dw, db);
-    return launched("k_linear_wgrad_rows launch");
-}
-
-int syn_masked_smooth_l1(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
-                         float* part, const int32_t* poison_flag, float* loss, void* stream) {
-    if (!target || !out || !mask || !loss || !part || batch <= 0 || channels <= 0 || channels % 64 || t_len <= 0 || t_len > 64)
-        return fail_msg("syn_masked_smooth_l1: channels must be a multiple of 64, t_len <= 64, part [batch][channels / 64]");
-    const int chunks = channels / 64;
-    hipLaunchKernelGGL(glu::k_sl1_tiles<false>, dim3(chunks, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
-                       (const float*)nullptr, part, (float*)nullptr);
-    hipLaunchKernelGGL(glu::k_sl1_final, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, mask, batch, chunks, channels, t_len, poison_flag, loss);
-    return launched("k_sl1_tiles launch");
-}
-
-int syn_masked_smooth_l1_grad(const float* target, const float* out, const uint8_t* mask, int32_t batch, int32_t channels, int32_t t_len, int32_t out_rows,
-                              const float* sample_scale, float* dout, void* stream) {
-    if (!target || !out || !mask || !dout || batch <= 0 || channels <= 0 || channels % 64 || t_len <= 0 || t_len > 64)
-        return fail_msg("syn_masked_smooth_l1_grad: channels must be a multiple of 64, t_len <= 64");
-    hipLaunchKernelGGL(glu::k_sl1_tiles<true>, dim3(channels / 64, batch), dim3(256), 0, (hipStream_t)stream, target, out, mask, channels, t_len, out_rows,
-                       sample_scale, (float*)nullptr, dout);
-    return launched("k_sl1_tiles (gradient) launch");
-}
-
-int syn_rows_concat_bf16(const syn_concat_src* srcs, int32_t n_src, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
-    if (!srcs || n_src < 1 || n_src > SYN_CONCAT_MAX || m_rows <= 0 || out_ld <= 0 || out_ld % 4 || !out_bf16) return fail_msg("syn_rows_concat_bf16: 1 .. 4 sources, out_ld % 4 == 0");
-    glu::CatArgs a;
-    memset(&a, 0, sizeof(a));
-    int total = 0;
-    for (int i = 0; i < n_src; ++i) {
-        const syn_concat_src& c = srcs[i];
-        if (!c.p || c.width <= 0 || c.width % 4 || c.ld % 4 || c.ld < c.width || c.row_div < 1 || c.pool < 1 || (c.pool > 1 && (c.row_div != 1 || c.p2)))
-            return fail_msg("syn_rows_concat_bf16: a source needs width % 4 == 0, ld % 4 == 0, ld >= width, row_div >= 1, pool >= 1 (a pooled source: row_div 1, no addend)");
-        a.s[i].p = c.p; a.s[i].p2 = c.p2; a.s[i].width = c.width; a.s[i].ld = c.ld; a.s[i].row_div = c.row_div; a.s[i].pool = c.pool;
-        total += c.width;
-    }
-    if (total > out_ld) return fail_msg("syn_rows_concat_bf16: the sources are wider than out_ld");
-    a.n_src = n_src; a.M = m_rows; a.out_ld = out_ld; a.out = (__bf16*)out_bf16;
-    const long n = (long)m_rows * (out_ld / 4);
-    hipLaunchKernelGGL(glu::k_rows_concat_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return launched("k_rows_concat_bf16 launch");
-}
-
-int syn_embed_rows_bf16(const int64_t* ids, const float* table, int32_t vocab, int32_t dim, int32_t m_rows, int32_t out_ld, void* out_bf16, void* stream) {
-    if (!ids || !table || !out_bf16 || vocab <= 0 || dim <= 0 || dim % 4 || m_rows <= 0 || out_ld < dim || out_ld % 4) return fail_msg("syn_embed_rows_bf16: dim % 4 == 0, out_ld >= dim, out_ld % 4 == 0");
-    const long n = (long)m_rows * (out_ld / 4);
-    hipLaunchKernelGGL(glu::k_embed_rows_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long*>(ids), table, vocab,
-                       dim, m_rows, out_ld, (__bf16*)out_bf16);
-    return launched("k_embed_rows_bf16 launch");
-}
-
-int syn_bct_to_rows_bf16(const float* x_bct, int32_t n_clips, int32_t channels, int32_t t_len, void* out_bf16, void* stream) {
-    if (!x_bct || !out_bf16 || n_clips <= 0 || channels <= 0 || channels % 64 || t_len != 32) return fail_msg("syn_bct_to_rows_bf16: channels % 64 == 0, t_len == 32");
-    hipLaunchKernelGGL(glu::k_bct_to_rows_bf16, dim3(channels / 64, n_clips), dim3(256), 0, (hipStream_t)stream, x_bct, channels, (__bf16*)out_bf16);
-    return launched("k_bct_to_rows_bf16 launch");
-}
-
-int syn_rows_group_sum(const float* src, int32_t ld, int32_t width, int32_t group, int32_t n_groups, float* out, void* stream) {
-    if (!src || !out || ld < width || width <= 0 || group <= 0 || n_groups <= 0) return fail_msg("syn_rows_group_sum: bad arguments");
-    hipLaunchKernelGGL(glu::k_rows_group_sum, dim3((n_groups * width + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, ld, width, group, n_groups, out);
-    return launched("k_rows_group_sum launch");
-}
-
-int syn_rows_expand(const float* src, int32_t ld, int32_t width, int32_t row_div, float scale, int32_t m_rows, float* out, void* stream) {
-    if (!src || !out || width <= 0 || width % 4 || ld < width || ld % 4 || row_div < 1 || m_rows <= 0) return fail_msg("syn_rows_expand: width % 4 == 0, ld >= width, ld % 4 == 0, row_div >= 1");
-    const long n = (long)m_rows * (width / 4);
-    hipLaunchKernelGGL(glu::k_rows_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, ld, width, row_div, scale, m_rows, out);
-    return launched("k_rows_expand launch");
-}
-
-int syn_colsum_parts(const float* part, int32_t rows, int32_t n, float* out, void* stream) {
-    if (!part || !out || rows <= 0 || n <= 0) return fail_msg("syn_colsum_parts: bad arguments");
-    hipLaunchKernelGGL(glu::k_colsum_parts, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, part, rows, n, out);
-    return launched("k_colsum_parts launch");
-}
-
-int syn_touch(const void* p, int64_t bytes, void* stream) {
-    if (!p || bytes < 64) return fail_msg("syn_touch: at least one 64-byte line");
-    const long lines = bytes / 64;
-    const long blocks = (lines + 255) / 256;
-    hipLaunchKernelGGL(glu::k_touch, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)p, lines, (unsigned*)nullptr);
-    return launched("k_touch launch");
-}
-
 int syn_rotary(const float* x, const float* cos_t, const float* sin_t, int32_t n_seq, int32_t inverse, float* y, void* stream) {
     if (!x || !cos_t || !sin_t || !y || n_seq <= 0) return fail_msg("syn_rotary: null pointer / empty batch");
     const long n_tok = (long)n_seq * SYN_T;
     hipLaunchKernelGGL(trn::k_rotary, dim3((unsigned)((n_tok * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, cos_t, sin_t, n_tok, inverse, y);
     return launched("k_rotary launch");
-}
-
-int32_t syn_bn_chunks(int64_t rows) { const int cr = trn::bn_chunk_rows((long)rows); return (int32_t)((rows + cr - 1) / cr); }
-
-int syn_bn_act_fwd(const float* y, const float* shortcut, int64_t rows, int32_t channels, const float* gamma, const float* beta, float eps,
-                   float momentum, float* run_mean, float* run_var, const float* conv_bias, int32_t act, float* ws, int32_t ws_chunks, float* stats,
-                   float* z, void* stream) {
-    if (!y || !gamma || !beta || !ws || !stats || !z || rows <= 0 || channels <= 0 || channels % 4 || 256 % (channels / 4) || channels > 1024)
-        return fail_msg("syn_bn_act_fwd: need channels in {4 .. 1024} with channels / 4 dividing 256, rows > 0, non-null pointers");
-    hipStream_t s = (hipStream_t)stream;
-    // ws_chunks > 0: ws already holds that many [2][channels] partial sums (written by the convolution's epilogue, syn_conv1d_train_fwd)
-    const int chunks = ws_chunks > 0 ? ws_chunks : syn_bn_chunks(rows);
-    if (ws_chunks <= 0) hipLaunchKernelGGL(trn::k_bn_stats, dim3(chunks), dim3(256), 0, s, y, (long)rows, channels, ws);
-    hipLaunchKernelGGL(trn::k_bn_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, (long)rows, eps, momentum,
-                       stats, run_mean, run_var, conv_bias);
-    const long n4 = rows * channels / 4;
-    hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
-                       act, z);
-    return launched("syn_bn_act_fwd");
-}
-
-int syn_bn_act_bwd(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
-                   int32_t channels, int32_t act, float* ws, float* dgamma_dbeta, float* dy, float* dshortcut, void* stream) {
-    if (!dz || !y || !stats || !gamma || !ws || !dgamma_dbeta || !dy || rows <= 0 || channels % 4 || 256 % (channels / 4))
-        return fail_msg("syn_bn_act_bwd: bad arguments");
-    if (act && !z && (dshortcut || !beta)) return fail_msg("syn_bn_act_bwd: z may only be omitted (with beta given) when no shortcut entered the activation");
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = syn_bn_chunks(rows);
-    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
-    hipLaunchKernelGGL(trn::k_bn_bwd_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgamma_dbeta);
-    const long n4 = rows * channels / 4;
-    hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)dgamma_dbeta,
-                       channels, n4, (long)rows, act, dy, dshortcut);
-    return launched("syn_bn_act_bwd");
-}
-
-/* ---- the fused tail of a BasicBlock (syn_train.inc): statistics -> per-channel affine; one elementwise pass per block and direction ---- */
-static bool bn_shape_ok(int64_t rows, int32_t channels) { return rows > 0 && channels > 0 && channels % 4 == 0 && 256 % (channels / 4) == 0 && channels <= 1024; }
-
-int syn_bn_finalize(const float* part, int32_t chunks, int64_t rows, int32_t channels, const float* gamma, const float* beta, float eps, float momentum,
-                    float* run_mean, float* run_var, const float* conv_bias, float* stats, float* affine, void* stream) {
-    if (!part || chunks <= 0 || !gamma || !beta || !stats || !affine || !bn_shape_ok(rows, channels)) return fail_msg("syn_bn_finalize: bad arguments");
-    hipLaunchKernelGGL(trn::k_bn_finalize_aff, dim3(channels), dim3(256), 0, (hipStream_t)stream, part, chunks, channels, (long)rows, eps, momentum, gamma, beta,
-                       stats, affine, run_mean, run_var, conv_bias);
-    return launched("syn_bn_finalize");
-}
-
-int syn_bn_finalize_pair(const syn_bn_finalize_job* a, const syn_bn_finalize_job* b, void* stream) {
-    if (!a || !b) return fail_msg("syn_bn_finalize_pair: two jobs");
-    trn::FinJob j[2];
-    const syn_bn_finalize_job* q[2] = {a, b};
-    for (int i = 0; i < 2; ++i) {
-        if (!q[i]->part || q[i]->chunks <= 0 || !q[i]->gamma || !q[i]->beta || !q[i]->stats || !q[i]->affine || !bn_shape_ok(q[i]->rows, q[i]->channels))
-            return fail_msg("syn_bn_finalize_pair: bad arguments");
-        j[i].part = q[i]->part; j[i].chunks = q[i]->chunks; j[i].C = q[i]->channels; j[i].rows = (long)q[i]->rows; j[i].eps = q[i]->eps; j[i].momentum = q[i]->momentum;
-        j[i].gamma = q[i]->gamma; j[i].beta = q[i]->beta; j[i].stats = q[i]->stats; j[i].aff = q[i]->affine;
-        j[i].run_mean = q[i]->run_mean; j[i].run_var = q[i]->run_var; j[i].conv_bias = q[i]->conv_bias;
-    }
-    hipLaunchKernelGGL(trn::k_bn_finalize_aff2, dim3(j[0].C + j[1].C), dim3(256), 0, (hipStream_t)stream, j[0], j[1]);
-    return launched("syn_bn_finalize_pair");
-}
-
-int syn_bn_apply2(const float* y, const float* affine, const float* shortcut, const float* short_affine, int64_t rows, int32_t channels, int32_t act,
-                  float* z, void* stream) {
-    if (!y || !affine || !z || !bn_shape_ok(rows, channels) || (short_affine && !shortcut)) return fail_msg("syn_bn_apply2: bad arguments");
-    const long n4 = rows * channels / 4;
-    hipLaunchKernelGGL(trn::k_bn_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, affine, shortcut, short_affine, channels, n4, act, z);
-    return launched("syn_bn_apply2");
-}
-
-int syn_bn_block_bwd(const float* dz, const float* y, const float* shortcut, const float* stats, const float* affine, const float* short_stats,
-                     const float* short_affine, int64_t rows, int32_t channels, int32_t act, float* ws, float* dgb, float* short_dgb, float* dy,
-                     float* dshortcut, void* stream) {
-    if (!dz || !y || !stats || !affine || !ws || !dgb || !bn_shape_ok(rows, channels)) return fail_msg("syn_bn_block_bwd: bad arguments");
-    if (!dy && dshortcut) return fail_msg("syn_bn_block_bwd: dy NULL (statistics and dgamma / dbeta only) takes no dshortcut either");
-    if ((short_affine != nullptr) != (short_stats != nullptr) || (short_affine && (!shortcut || !short_dgb || (dy && !dshortcut))))
-        return fail_msg("syn_bn_block_bwd: a normalised shortcut needs its tensor, statistics, affine, gradient buffer and dshortcut");
-    if (dshortcut && !shortcut) return fail_msg("syn_bn_block_bwd: dshortcut without a shortcut");
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = syn_bn_chunks(rows);
-    hipLaunchKernelGGL(trn::k_bn_bwd_stats2, dim3(chunks), dim3(256), 0, s, dz, y, shortcut, stats, affine, short_stats, short_affine, (long)rows, channels, act, ws);
-    hipLaunchKernelGGL(trn::k_bn_bwd_finalize2, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgb, short_affine ? short_dgb : nullptr);
-    const long n4 = rows * channels / 4;
-    if (dy)                                                   // (dy NULL: the caller's next kernel forms dy / dshortcut itself - syn_conv1d_first_wgrad_tail)
-        hipLaunchKernelGGL(trn::k_bn_bwd_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, y, shortcut, stats, affine, short_stats, short_affine,
-                           (const float*)dgb, (const float*)short_dgb, channels, n4, (long)rows, act, dy, dshortcut);
-    return launched("syn_bn_block_bwd");
-}
-
-/* ---- nn.SyncBatchNorm on the same kernels: sums -> (the caller's all-reduce) -> apply ---- */
-int syn_bn_sums(const float* y, int64_t rows, int32_t channels, float* ws, int32_t ws_chunks, double* sums, void* stream) {
-    if (!ws || !sums || rows <= 0 || channels <= 0 || channels % 4 || 256 % (channels / 4) || channels > 1024 || (ws_chunks <= 0 && !y))
-        return fail_msg("syn_bn_sums: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = ws_chunks > 0 ? ws_chunks : syn_bn_chunks(rows);
-    if (ws_chunks <= 0) hipLaunchKernelGGL(trn::k_bn_stats, dim3(chunks), dim3(256), 0, s, y, (long)rows, channels, ws);
-    hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
-    return launched("syn_bn_sums");
-}
-
-int syn_bn_act_apply(const float* y, const float* shortcut, int64_t rows, int64_t rows_total, int32_t channels, const float* gamma, const float* beta,
-                     float eps, float momentum, float* run_mean, float* run_var, const float* conv_bias, int32_t act, const double* sums_total,
-                     float* stats, float* z, void* stream) {
-    if (!y || !gamma || !beta || !sums_total || !stats || !z || rows <= 0 || rows_total < rows || channels <= 0 || channels % 4)
-        return fail_msg("syn_bn_act_apply: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(trn::k_bn_finalize64, dim3((channels + 255) / 256), dim3(256), 0, s, sums_total, channels, (long)rows_total, eps, momentum, stats,
-                       run_mean, run_var, conv_bias);
-    const long n4 = rows * channels / 4;
-    hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
-                       act, z);
-    return launched("syn_bn_act_apply");
-}
-
-int syn_bn_bwd_sums(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
-                    int32_t channels, int32_t act, float* ws, double* sums, void* stream) {
-    if (!dz || !y || !stats || !gamma || !ws || !sums || rows <= 0 || channels % 4 || 256 % (channels / 4))
-        return fail_msg("syn_bn_bwd_sums: bad arguments");
-    if (act && !z && !beta) return fail_msg("syn_bn_bwd_sums: z may only be omitted with beta given");
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = syn_bn_chunks(rows);
-    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
-    hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
-    return launched("syn_bn_bwd_sums");
-}
-
-int syn_bn_act_bwd_apply(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta,
-                         const double* sums_local, const double* sums_total, int64_t rows, int64_t rows_total, int32_t channels, int32_t act,
-                         float* dgamma_dbeta, float* scratch, float* dy, float* dshortcut, void* stream) {
-    if (!dz || !y || !stats || !gamma || !sums_local || !sums_total || !dgamma_dbeta || !scratch || !dy || rows <= 0 || rows_total < rows || channels % 4)
-        return fail_msg("syn_bn_act_bwd_apply: bad arguments");
-    if (act && !z && (dshortcut || !beta)) return fail_msg("syn_bn_act_bwd_apply: z may only be omitted (with beta given) when no shortcut entered the activation");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(trn::k_bn_bwd_unpack64, dim3((channels + 255) / 256), dim3(256), 0, s, sums_local, sums_total, channels, dgamma_dbeta, scratch);
-    const long n4 = rows * channels / 4;
-    hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)scratch,
-                       channels, n4, (long)rows_total, act, dy, dshortcut);
-    return launched("syn_bn_act_bwd_apply");
-}
-
-int syn_linear_bwd_prep(const float* dy, int32_t ld, int32_t row_div, float const_scale, int32_t m_rows, int32_t n, const float* row_scale,
-                        int32_t rows_per_scale, void* dy_bf16, void* dy_bf16_t, float* colsum_part, void* stream) {
-    if (!dy || !dy_bf16 || !dy_bf16_t || m_rows <= 0 || n <= 0 || m_rows % 64 || n % 64 || (row_scale && rows_per_scale <= 0) || ld < n || ld % 4 || row_div < 1)
-        return fail_msg("syn_linear_bwd_prep: need m_rows % 64 == 0, n % 64 == 0, ld >= n, ld % 4 == 0, row_div >= 1 and non-null pointers");
-    hipLaunchKernelGGL(trn::k_linear_bwd_prep, dim3(n / 64, m_rows / 64), dim3(256), 0, (hipStream_t)stream, dy, ld, row_div, const_scale, m_rows, n, row_scale,
-                       rows_per_scale, (__bf16*)dy_bf16, (__bf16*)dy_bf16_t, colsum_part);
-    return launched("k_linear_bwd_prep launch");
-}
-
-// ---- optimizer step (clip + Adam) over lists of <= 64 tensors ------------------------------------------------------------------------------------
-static int opt_fill(trn::OptList& L, const syn_opt_list* l, const char* who) {
-    static_assert(SYN_OPT_MAX == trn::kOptMax, "include/syn_hip.h: tensors per optimizer list");
-    if (!l || l->n <= 0 || l->n > SYN_OPT_MAX) return fail_msg(who);
-    int blocks = 0;
-    for (int i = 0; i < l->n; ++i) {
-        if (!l->g[i] || l->numel[i] <= 0) return fail_msg(who);
-        L.p[i] = l->p[i]; L.g[i] = l->g[i]; L.m[i] = l->m[i]; L.v[i] = l->v[i]; L.numel[i] = l->numel[i];
-        L.first[i] = blocks;
-        blocks += (l->numel[i] + trn::kOptChunk - 1) / trn::kOptChunk;
-    }
-    L.first[l->n] = blocks; L.n = l->n;
-    return 0;
-}
-
-int32_t syn_opt_blocks(const syn_opt_list* l) {
-    if (!l || l->n <= 0 || l->n > SYN_OPT_MAX) return -1;
-    int blocks = 0;
-    for (int i = 0; i < l->n; ++i) blocks += (l->numel[i] + trn::kOptChunk - 1) / trn::kOptChunk;
-    return blocks;
-}
-
-int syn_opt_sqnorm(const syn_opt_list* l, float* partials, void* stream) {
-    trn::OptList L;
-    if (!partials) return fail_msg("syn_opt_sqnorm: partials is NULL");
-    if (int rc = opt_fill(L, l, "syn_opt_sqnorm: need 1 .. 64 tensors with gradients")) return rc;
-    hipLaunchKernelGGL(trn::k_opt_sqnorm, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, partials);
-    return launched("k_opt_sqnorm launch");
-}
-
-int syn_opt_scalars(const float* partials, int32_t n_partials, float max_norm, const float* lr_dev, float lr, float beta1, float beta2, float* step_dev,
-                    float* scal4, void* stream) {
-    if ((n_partials > 0 && !partials) || n_partials < 0 || !step_dev || !scal4) return fail_msg("syn_opt_scalars: bad arguments");
-    hipLaunchKernelGGL(trn::k_opt_scalars, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, max_norm, lr_dev, lr, beta1, beta2, step_dev, scal4);
-    return launched("k_opt_scalars launch");
-}
-
-int syn_opt_adam(const syn_opt_list* l, const float* scal4, float beta1, float beta2, float eps, float weight_decay, void* stream) {
-    trn::OptList L;
-    if (!scal4) return fail_msg("syn_opt_adam: scal4 is NULL");
-    if (int rc = opt_fill(L, l, "syn_opt_adam: need 1 .. 64 tensors")) return rc;
-    for (int i = 0; i < L.n; ++i) if (!L.p[i] || !L.m[i] || !L.v[i]) return fail_msg("syn_opt_adam: null parameter / moment pointer");
-    hipLaunchKernelGGL(trn::k_opt_adam, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, scal4, beta1, beta2, eps, weight_decay);
-    return launched("k_opt_adam launch");
-}
-
-int syn_embedding_wgrad(const int64_t* ids, const float* dy, int32_t ld, int32_t n_pos, int32_t vocab, int32_t dim, float* dw, void* stream) {
-    if (!ids || !dy || !dw || n_pos <= 0 || n_pos > glu::kEmbMaxPos || vocab <= 0 || vocab > glu::kEmbMaxV || dim <= 0 || dim > glu::kEmbMaxD || ld < dim)
-        return fail_msg("syn_embedding_wgrad: bad arguments (at most 8192 positions per call, vocab <= 65536, dim <= 512, ld >= dim)");
-    hipLaunchKernelGGL(glu::k_embedding_wgrad, dim3((n_pos + glu::kEmbWaves - 1) / glu::kEmbWaves), dim3(glu::kEmbWaves * 64), 0, (hipStream_t)stream,
-                       reinterpret_cast<const long*>(ids), dy, ld, n_pos, vocab, dim, dw);
-    return launched("k_embedding_wgrad launch");
-}
-
-int syn_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
-    if (!x || !dy || !dx || n <= 0 || n % 4) return fail_msg("syn_gelu_bwd: n must be a positive multiple of 4");
-    hipLaunchKernelGGL(trn::k_gelu_bwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, (size_t)(n / 4));
-    return launched("k_gelu_bwd launch");
-}
-
-int syn_attn_fwd(const float* qkv, float* o, void* o_bf16, int32_t n_seq, void* stream) {
-    if (!qkv || (!o && !o_bf16) || n_seq <= 0) return fail_msg("syn_attn_fwd: bad arguments");
-    hipLaunchKernelGGL(trn::k_attn_fwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnFwd2Lds, (hipStream_t)stream, qkv, o, (__bf16*)o_bf16);
-    return launched("k_attn_fwd launch");
-}
-
-int syn_attn_bwd(const float* qkv, const float* d_o, float* dqkv, int32_t n_seq, void* stream) {
-    if (!qkv || !d_o || !dqkv || n_seq <= 0) return fail_msg("syn_attn_bwd: bad arguments");
-    static OncePerDevice once;
-    if (once.first()) allow_lds(trn::k_attn_bwd2, trn::kAttnBwd2Lds);
-    hipLaunchKernelGGL(trn::k_attn_bwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnBwd2Lds, (hipStream_t)stream, qkv, d_o, dqkv);
-    return launched("k_attn_bwd launch");
-}
-
-int syn_cond_encode(const syn_cond_weights* w, const float* audio_feat, const int64_t* word, const float* seed, const float* style,
-                    int32_t n_clips, float* d_scratch, float* cond, void* stream) {
-    if (!w || !w->gt || !w->tw || !w->st || !w->c0 || !audio_feat || !word || !seed || !d_scratch || !cond || n_clips <= 0)
-        return fail_msg("syn_cond_encode: null argument");
-    if (w->seed_dim <= 0 || w->style_dim < 0 || w->vocab <= 0 || (w->style_dim > 0 && !style))
-        return fail_msg("syn_cond_encode: bad dimensions (a model with a style projection needs the style vectors)");
-    hipStream_t s = (hipStream_t)stream;
-    static_assert(cnd::kClipSplit == SYN_COND_SCRATCH_ROWS, "include/syn_hip.h: d_scratch rows per clip");
-    hipLaunchKernelGGL(cnd::k_cond_clip, dim3(SYN_D / 64, (n_clips + 31) / 32, cnd::kClipSplit), dim3(256), 0, s, seed, w->seed_dim, style,
-                       w->style_dim, w->st, n_clips, d_scratch);
-    hipLaunchKernelGGL(cnd::k_cond_frames, dim3(SYN_D / 128, n_clips), dim3(256), 0, s, audio_feat, (const long long*)word, w->gt, w->tw,
-                       w->vocab, d_scratch, w->c0, n_clips, cond);
-    return launched("syn_cond_encode");
-}
-
-int32_t syn_wav_out_frames(int32_t n_samples) { return n_samples >= 15 ? wav_plan(n_samples).L4 : 0; }
-
-int64_t syn_wav_workspace_bytes(int32_t n_clips, int32_t n_samples) {
-    if (n_clips <= 0 || n_samples < 15) return 0;
-    return (int64_t)wav_plan(n_samples).per_clip * n_clips * 2;
-}
-
-int syn_wav_encode(const syn_wavenc* enc, const float* wav_in, int32_t n_clips, int32_t n_samples, void* workspace, float* out,
-                   void* stream) {
-    if (!enc || !wav_in || !workspace || !out || n_clips <= 0) return fail_msg("syn_wav_encode: null argument");
-    if (enc->cin != 1 && enc->cin != 2) return fail_msg("syn_wav_encode: 1 or 2 input channels");
-    const WavPlan p = wav_plan(n_samples);
-    if (p.L4 <= 0) return fail_msg("syn_wav_encode: clip too short");
-    hipStream_t s = (hipStream_t)stream;
-    __bf16* const ws = (__bf16*)workspace;
-    const long cs = p.per_clip;
-    int rc;
-    {   // block 0 in one kernel: conv1 recomputed into the LDS tile, shortcut as the accumulators' initial value
-        static OncePerDevice once;
-        if (once.first()) { allow_lds(wav::k_block0, wav::kB0Lds); }
-        wav::B0Args b;
-        b.wav = wav_in; b.wav_clip_stride = (long)n_samples * enc->cin; b.L = n_samples; b.cin = enc->cin; b.L1 = p.L1;
-        b.w_first = enc->w_first; b.W2 = (const uint4*)enc->conv[0].w; b.bias2 = enc->conv[0].bias;
-        b.X1 = ws + p.x1; b.x1_clip_stride = cs;
-        hipLaunchKernelGGL(wav::k_block0, dim3((p.L1 + wav::kB0Tile - 1) / wav::kB0Tile, n_clips), dim3(wav::kB0Waves * 64), wav::kB0Lds, s, b);
-    }
-    auto base = [&](int i) {
-        wav::CArgs a;
-        memset(&a, 0, sizeof(a));
-        a.W = (const uint4*)enc->conv[i].w; a.bias = enc->conv[i].bias;
-        a.x_clip_stride = a.z_clip_stride = a.s_clip_stride = a.r_clip_stride = cs;
-        return a;
-    };
-    wav::CArgs a;
-    // block 1: conv1 | shortcut (stride 6 = 3 taps over 6-row groups), conv2 -> x2 (halo: block 2 pads by 7)
-    a = base(1); a.X = ws + p.x1; a.x_rows = (p.L1 + 5) / 6; a.L_out = p.L2; a.Z = ws + p.z1; a.z_off = kHalo * 64; a.S = ws + p.s1;
-    if ((rc = launch_conv<384, 3, 2, 2, 2, wav::E_C1SC>(a, n_clips, s))) return rc;
-    a = base(2); a.X = ws + p.z1; a.x_rows = p.L2 + 2 * kHalo; a.L_out = p.L2; a.Z = ws + p.x2; a.z_off = kHalo * 64; a.R = ws + p.s1;
-    if ((rc = launch_conv<64, 15, 1, 4, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    // block 2 (identity shortcut): conv1, conv2 + x2 -> x3
-    a = base(3); a.X = ws + p.x2; a.x_rows = p.L2 + 2 * kHalo; a.L_out = p.L2; a.Z = ws + p.z2; a.z_off = kHalo * 64;
-    if ((rc = launch_conv<64, 15, 1, 4, 4, wav::E_C1>(a, n_clips, s))) return rc;
-    a = base(4); a.X = ws + p.z2; a.x_rows = p.L2 + 2 * kHalo; a.L_out = p.L2; a.Z = ws + p.x3; a.R = ws + p.x2; a.r_off = kHalo * 64;
-    if ((rc = launch_conv<64, 15, 1, 4, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    // block 3: 64 -> 128, stride 6
-    a = base(5); a.X = ws + p.x3; a.x_rows = (p.L2 + 5) / 6; a.L_out = p.L3; a.Z = ws + p.z3; a.z_off = kHalo * 128; a.S = ws + p.s3;
-    if ((rc = launch_conv<384, 3, 4, 1, 4, wav::E_C1SC>(a, n_clips, s))) return rc;
-    a = base(6); a.X = ws + p.z3; a.x_rows = p.L3 + 2 * kHalo; a.L_out = p.L3; a.Z = ws + p.x4; a.z_off = kHalo * 128; a.R = ws + p.s3;
-    if ((rc = launch_conv<128, 15, 2, 2, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    // block 4 (identity shortcut)
-    a = base(7); a.X = ws + p.x4; a.x_rows = p.L3 + 2 * kHalo; a.L_out = p.L3; a.Z = ws + p.z4; a.z_off = kHalo * 128;
-    if ((rc = launch_conv<128, 15, 2, 2, 4, wav::E_C1>(a, n_clips, s))) return rc;
-    a = base(8); a.X = ws + p.z4; a.x_rows = p.L3 + 2 * kHalo; a.L_out = p.L3; a.Z = ws + p.x5; a.R = ws + p.x4; a.r_off = kHalo * 128;
-    if ((rc = launch_conv<128, 15, 2, 2, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    // block 5: 128 -> 256, stride 3 (5 taps over 3-row groups); conv2 writes the fp32 result
-    a = base(9); a.X = ws + p.x5; a.x_rows = (p.L3 + 2) / 3; a.L_out = p.L4; a.Z = ws + p.z5; a.z_off = kHalo * 256; a.S = ws + p.s5;
-    if ((rc = launch_conv<384, 5, 8, 1, 4, wav::E_C1SC>(a, n_clips, s))) return rc;
-    a = base(10); a.X = ws + p.z5; a.x_rows = p.L4 + 2 * kHalo; a.L_out = p.L4; a.R = ws + p.s5; a.Yf = out; a.yf_clip_stride = (long)p.L4 * 256;
-    if ((rc = launch_conv<256, 15, 4, 1, 4, wav::E_C2>(a, n_clips, s))) return rc;
-    return launched("syn_wav_encode");
-}
-
-// output-channel tile of the strided layers' weight gradient (k_conv_wgrad_s<CO_T, TAPS>; conv_train_wgrad_impl launches what this says)
-static int wgrad_s_tile(int cout) { return cout >= 64 ? 64 : 0; }   // (128-channel tiles for block 3 meant 3 slices x 85 shares of 590 KB; 64: 6 x 42)
-
-int32_t syn_conv1d_wgrad_shares(int32_t n_clips, int32_t l_out, int32_t cin_rows, int32_t cout) {
-    if (n_clips <= 0 || l_out <= 0 || cin_rows < 16 || cout < 64 || cout % 64) return 0;   // (a size query: 0 for a geometry no kernel takes, as the other queries answer)
-    const int chunks = n_clips * ((l_out + wav::kWgP - 1) / wav::kWgP);
-    const bool strided = cin_rows == 384;                           // (the stride-1 layers have 64 / 128 / 256 row channels)
-    // slices of the gradient = workgroups per position share (stride-1 layers: cout = cin; 64 channels: one 64 x 64 slice)
-    int blocks = strided ? (cin_rows / wav::kWsJ) * (cout / wgrad_s_tile(cout)) : cin_rows / (16 * wav::wgrad_cb(cin_rows));
-    if (!strided && cin_rows >= 128) blocks = (cin_rows / (16 * kWgradWideCb)) * (cin_rows / 64);   // (64-channel output tiles: launch_wgrad_tiled)
-    if (!strided && cin_rows == 64 && wgrad64_two_slices(l_out)) blocks = 2;
-    if (blocks < 1) return 0;
-    int shares = strided ? device_cus() / blocks : (device_cus() + blocks - 1) / blocks;   // one workgroup per CU in total (the partial sums are read back once per share)
-    if (shares > chunks) shares = chunks;
-    // every share writes a partial sum of the whole gradient block and k_conv_wgrad_sum reads them all back: with few chunks per
-    // share that traffic outweighs the parallelism (time ~ chunks / shares x t_chunk + shares x t_partial, t_chunk / t_partial ~ 60)
-    // (r5b: 21 -> 60 - the chunk got 1.4 x faster (streamed x rows), the partial sums did not: 608 chunks on 112 shares 57 us, on 155 - 220 shares 47 - 48 us)
-    const int balanced = (int)sqrtf(60.f * (float)chunks);
-    if (!strided && shares > balanced) shares = balanced;
-    return shares < 1 ? 1 : shares;
-}
-
-static int conv_train_wgrad_impl(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                                 int32_t cout, const float* in_affine, int32_t in_act, float* ws, float* dw, void* stream) {
-    if (!x || !dy || !ws || n_clips <= 0 || l_in <= 0 || cin % 16 || stride < 1) return fail_msg("syn_conv1d_train_wgrad: bad arguments");
-    if (in_affine && stride != 1) return fail_msg("syn_conv1d_train_wgrad_norm: the input affine is for the stride-1 layers (conv2 of a block)");
-    if (!((stride == 1 && pad == 7) || (pad == 0 && stride * cin == 384 && (stride == 3 || stride == 6))))
-        return fail_msg("syn_conv1d_train_wgrad: stride 1 with padding 7, or the encoder's unpadded strided layers (stride x cin = 384)");
-    const int l_out = (l_in + 2 * pad - 15) / stride + 1, taps = (15 + stride - 1) / stride, cinp = stride * cin;
-    if (l_out <= 0) return fail_msg("syn_conv1d_train_wgrad: input shorter than the kernel");
-    wav::WArgs a;
-    a.GY = dy; a.gy_clip_stride = (long)l_out * cout; a.L_out = l_out; a.X = x; a.x_clip_stride = (long)l_in * cin; a.x_elems = (long)l_in * cin;
-    a.cin = cinp; a.co_n = cout; a.n_clips = n_clips; a.chunks_per_clip = (l_out + wav::kWgP - 1) / wav::kWgP; a.row0 = stride == 1 ? -7 : 0;
-    a.shares = syn_conv1d_wgrad_shares(n_clips, l_out, cinp, cout); a.part = ws;
-    a.in_aff = in_affine; a.in_act = in_act; a.GY2 = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (cout == 64 && taps == 15 && wgrad64_two_slices(l_out)) rc = launch_wgrad_tiled<64, 15, 2>(a, s);
-    else if (cout == 64 && taps == 15) rc = launch_wgrad<64, 15>(a, s);
-    else if ((cout == 128 || cout == 256) && taps == 15) rc = launch_wgrad_tiled<64, 15, kWgradWideCb>(a, s);
-    // the strided layers, read as stride-1 ones over rows of stride * Cin = 384 channels: waves = row channels, not taps
-    else if (cout == 64 && taps == 3) rc = launch_wgrad_s<64, 3>(a, s);
-    else if (cout == 128 && taps == 3) rc = launch_wgrad_s<64, 3>(a, s);      // (two 64-channel tiles: twice the slices, half the shares)
-    else if (cout == 256 && taps == 5) rc = launch_wgrad_s<64, 5>(a, s);     // (128-channel blocks spill: 20 accumulator tiles per wave is the limit)
-    else return fail_msg("syn_conv1d_train_wgrad: 64 / 128 / 256 output channels; strided: (64 | 128, stride 6), (256, stride 3)");
-    if (rc || !dw) return rc;                                    // (dw NULL: the partial sums only - syn_conv1d_wgrad_sums adds several gradients' up in one launch)
-    const int total4 = cout * taps * cinp / 4;                   // (cin % 16 == 0: four consecutive channels share r)
-    hipLaunchKernelGGL(wav::k_conv_wgrad_sum, dim3((total4 + 31) / 32), dim3(256), 0, s, (const float*)ws, a.shares, cout, cin, stride, taps, dw);
-    return launched("k_conv_wgrad_sum launch");
-}
-
-int syn_conv1d_train_wgrad(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                           int32_t cout, float* ws, float* dw, void* stream) {
-    return conv_train_wgrad_impl(x, dy, n_clips, l_in, cin, stride, pad, cout, nullptr, 0, ws, dw, stream);
-}
-
-int syn_conv1d_train_wgrad_norm(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                                int32_t cout, const float* in_affine, int32_t in_act, float* ws, float* dw, void* stream) {
-    if (!in_affine) return fail_msg("syn_conv1d_train_wgrad_norm: in_affine is NULL (use syn_conv1d_train_wgrad)");
-    return conv_train_wgrad_impl(x, dy, n_clips, l_in, cin, stride, pad, cout, in_affine, in_act, ws, dw, stream);
-}
-
-/* conv1 and the shortcut convolution of a down-sampling block (same input, same geometry): both weight gradients' partial sums from ONE launch that stages the
- * input once (k_conv_wgrad_s<128, 3, true>: the tile's two halves are the two dy).  (64, 6, 64) only - block 1, whose input is the encoder's largest tensor. */
-int syn_conv1d_train_wgrad_pair(const float* x, const float* dy_a, const float* dy_b, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                                int32_t cout, float* ws, void* stream) {
-    if (!x || !dy_a || !dy_b || !ws || n_clips <= 0 || l_in <= 0) return fail_msg("syn_conv1d_train_wgrad_pair: bad arguments");
-    if (!(cin == 64 && stride == 6 && pad == 0 && cout == 64)) return fail_msg("syn_conv1d_train_wgrad_pair: the (64, stride 6, 64) layer pair only (block 1 of the audio encoder)");
-    const int l_out = (l_in - 15) / stride + 1, cinp = stride * cin;
-    if (l_out <= 0) return fail_msg("syn_conv1d_train_wgrad_pair: input shorter than the kernel");
-    wav::WArgs a;
-    a.GY = dy_a; a.GY2 = dy_b; a.gy_clip_stride = (long)l_out * cout; a.L_out = l_out; a.X = x; a.x_clip_stride = (long)l_in * cin; a.x_elems = (long)l_in * cin;
-    a.cin = cinp; a.co_n = cout; a.n_clips = n_clips; a.chunks_per_clip = (l_out + wav::kWgP - 1) / wav::kWgP; a.row0 = 0;
-    a.shares = syn_conv1d_wgrad_shares(n_clips, l_out, cinp, cout); a.part = ws;          // (3 slices, as for one of the two: ws holds shares x 2 gradients)
-    a.in_aff = nullptr; a.in_act = 0;
-    return launch_wgrad_s<128, 3, true>(a, (hipStream_t)stream);
-}
-
-// workgroups of the persistent first-layer weight gradient (k_conv_first_wgrad_m): four per CU once there is that much work, never more than there are
-// 64-pair work items per workgroup
-static int first_wgrad_groups(int n_clips, int l_out, int per_cu = 4) {
-    const long pairs = (long)n_clips * ((l_out + 1) / 2);
-    const long want = (long)per_cu * device_cus(), by_work = (pairs + 255) / 256;      // (1 / 2 / 4 / 8 per CU at the bench shape: 190 / 123 / 108 / 107 us for the two launches)
-    return (int)(by_work < 1 ? 1 : by_work < want ? by_work : want);
-}
-int32_t syn_conv1d_first_parts(int32_t n_clips, int32_t l_out) {
-    return n_clips > 0 && l_out > 0 ? first_wgrad_groups(n_clips, l_out) : 0;        // one partial gradient per workgroup
-}
-int32_t syn_conv1d_first_tiles(int32_t n_clips, int32_t l_out) { return n_clips > 0 && l_out > 0 ? n_clips * ((l_out + wav::kF1Tile - 1) / wav::kF1Tile) : 0; }
-
-static int first_layer_args(wav::FArgs& a, const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, const char* who) {
-    if (!x || n_clips <= 0 || l_in <= 0 || (cin != 1 && cin != 2) || stride < 1 || stride > 8 || pad < 0) return fail_msg(who);
-    a.X = x; a.L_in = l_in; a.n_clips = n_clips; a.stride = stride; a.pad = pad;
-    a.L_out = (l_in + 2 * pad - 15) / stride + 1;
-    if (a.L_out <= 0) return fail_msg(who);
-    a.W = nullptr; a.Y = nullptr; a.DY = nullptr; a.part = nullptr; a.chunks_per_clip = (a.L_out + wav::kF1Chunk - 1) / wav::kF1Chunk;
-    a.BY = nullptr; a.bn_stats = a.bn_aff = a.bn_dgb = nullptr; a.bn_inv_rows = 0.f; a.bn_act = 0; a.W2 = nullptr; a.Y2 = nullptr; a.part2 = nullptr;
-    a.T_y2 = nullptr; a.t_stats = a.t_aff = a.t_dgb = nullptr; a.T_dy2 = nullptr;
-    return 0;
-}
-
-int syn_conv1d_first_fwd_stats(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, const float* w, float* y,
-                               float* bn_part, void* stream) {
-    wav::FArgs a;
-    if (!w || !y) return fail_msg("syn_conv1d_first_fwd: bad arguments");
-    if (int rc = first_layer_args(a, x, n_clips, l_in, cin, stride, pad, "syn_conv1d_first_fwd: bad arguments (cin 1 | 2, 64 output channels)")) return rc;
-    a.W = w; a.Y = y; a.part = bn_part;
-    const dim3 grid((a.L_out + wav::kF1Tile - 1) / wav::kF1Tile, n_clips);
-    size_t lds = (size_t)((wav::kF1Tile - 1) * stride + 15) * cin * sizeof(float);
-    if (lds < 4 * 2 * 64 * sizeof(float)) lds = 4 * 2 * 64 * sizeof(float);       // (the statistics of the four position groups meet in the window's place)
-    if (cin == 1) hipLaunchKernelGGL(wav::k_conv_first_fwd<1>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(wav::k_conv_first_fwd<2>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    return launched("k_conv_first_fwd launch");
-}
-
-int syn_conv1d_first_fwd(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, const float* w, float* y,
-                         void* stream) {
-    return syn_conv1d_first_fwd_stats(x, n_clips, l_in, cin, stride, pad, w, y, nullptr, stream);
-}
-
-struct FirstTail { const float* y2; const float* stats2; const float* aff2; const float* dgb2; float* dy2; };
-static int first_wgrad_impl(const float* x, const float* dy, const float* bn_y, const float* bn_stats, const float* bn_aff, const float* bn_dgb,
-                            int32_t bn_act, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws, float* dw, void* stream,
-                            const FirstTail* tail = nullptr) {
-    wav::FArgs a;
-    if (!dy || !ws) return fail_msg("syn_conv1d_first_wgrad: bad arguments");
-    if (int rc = first_layer_args(a, x, n_clips, l_in, cin, stride, pad, "syn_conv1d_first_wgrad: bad arguments (cin 1 | 2, 64 output channels)")) return rc;
-    a.DY = dy; a.part = ws;
-    if (bn_y) {
-        if (stride != 5 || !bn_stats || !bn_aff || !bn_dgb) return fail_msg("syn_conv1d_first_wgrad_bn: stride 5 (the encoder's), statistics, affine and dgamma / dbeta");
-        a.BY = bn_y; a.bn_stats = bn_stats; a.bn_aff = bn_aff; a.bn_dgb = bn_dgb; a.bn_inv_rows = 1.0f / ((float)n_clips * (float)a.L_out); a.bn_act = bn_act;
-    }
-    if (tail) {
-        if (!bn_y || !tail->y2 || !tail->stats2 || !tail->aff2 || !tail->dgb2 || !tail->dy2) return fail_msg("syn_conv1d_first_wgrad_tail: null pointer");
-        a.T_y2 = tail->y2; a.t_stats = tail->stats2; a.t_aff = tail->aff2; a.t_dgb = tail->dgb2; a.T_dy2 = tail->dy2;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int groups = first_wgrad_groups(n_clips, a.L_out);
-    if (tail) {
-        if ((long)n_clips * a.L_out * 64 >= (1L << 32)) return fail_msg("syn_conv1d_first_wgrad_tail: n_clips x l_out x 64 must stay below 2^32 elements");
-        if (cin == 1) hipLaunchKernelGGL((wav::k_conv_first_wgrad_m<1, true>), dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-        else hipLaunchKernelGGL((wav::k_conv_first_wgrad_m<2, true>), dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-    }
-    else if (cin == 1) hipLaunchKernelGGL((wav::k_conv_first_wgrad_m<1>), dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-    else hipLaunchKernelGGL((wav::k_conv_first_wgrad_m<2>), dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-    const int n = 64 * cin * 15;
-    if (dw) hipLaunchKernelGGL(wav::k_conv_first_wsum, dim3((n + 63) / 64), dim3(1024), 0, s, (const float*)ws, groups, n, dw);
-    return launched("k_conv_first_wgrad_m launch");
-}
-
-int syn_conv1d_wgrad_sums(const syn_wgrad_sum_job* jobs, int32_t n_jobs, void* stream) {
-    static_assert(SYN_WGRAD_SUM_MAX == wav::kWsumJobs, "include/syn_hip.h: jobs per syn_conv1d_wgrad_sums call");
-    if (!jobs || n_jobs < 1 || n_jobs > SYN_WGRAD_SUM_MAX) return fail_msg("syn_conv1d_wgrad_sums: 1 .. 4 jobs");
-    wav::WSumJobs a;
-    memset(&a, 0, sizeof(a));
-    int blocks = 0;
-    for (int i = 0; i < n_jobs; ++i) {
-        const syn_wgrad_sum_job& q = jobs[i];
-        wav::WSumJob& J = a.j[i];
-        if (!q.part || !q.dw || q.n_clips <= 0 || q.l_out <= 0) return fail_msg("syn_conv1d_wgrad_sums: null pointer / empty job");
-        J.part = q.part; J.dw = q.dw; J.cin = q.cin; J.stride = q.stride; J.co_n = q.cout; J.first_block = blocks;
-        if (q.first_layer) {
-            if ((q.cin != 1 && q.cin != 2) || q.cout != 64) return fail_msg("syn_conv1d_wgrad_sums: a first-layer job has 1 | 2 input and 64 output channels");
-            J.kind = 1; J.shares = first_wgrad_groups(q.n_clips, q.l_out); J.per = 64 * q.cin * 15; J.taps = 15;
-        } else {
-            if (q.cin % 16 || q.stride < 1) return fail_msg("syn_conv1d_wgrad_sums: cin must be a multiple of 16");
-            J.kind = 0; J.taps = (15 + q.stride - 1) / q.stride; J.shares = syn_conv1d_wgrad_shares(q.n_clips, q.l_out, q.stride * q.cin, q.cout);
-            J.per = q.cout * J.taps * q.stride * q.cin;
-        }
-        J.pitch = q.share_pitch > 0 ? q.share_pitch : J.per;
-        if (J.pitch < J.per || J.pitch % 4) return fail_msg("syn_conv1d_wgrad_sums: share_pitch must be 0 or a multiple of 4 not below the gradient's size");
-        blocks += (J.per / 4 + 31) / 32;
-    }
-    a.n = n_jobs;
-    hipLaunchKernelGGL(wav::k_conv_wgrad_sums, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return launched("k_conv_wgrad_sums launch");
-}
-
-int syn_conv1d_first_wgrad(const float* x, const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws,
-                           float* dw, void* stream) {
-    return first_wgrad_impl(x, dy, nullptr, nullptr, nullptr, nullptr, 0, n_clips, l_in, cin, stride, pad, ws, dw, stream);
-}
-
-int syn_conv1d_first_wgrad_bn(const float* x, const float* dz, const float* y, const float* stats, const float* affine, const float* dgamma_dbeta,
-                              int32_t act, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws, float* dw, void* stream) {
-    if (!y) return fail_msg("syn_conv1d_first_wgrad_bn: y is NULL (use syn_conv1d_first_wgrad)");
-    return first_wgrad_impl(x, dz, y, stats, affine, dgamma_dbeta, act, n_clips, l_in, cin, stride, pad, ws, dw, stream);
-}
-
-int syn_conv1d_first_wgrad_bn_lin(const float* x, const float* dz, const float* y, const float* stats, const float* affine, int32_t act,
-                                  int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws, float* dw, float* dgamma_dbeta, void* stream) {
-    wav::FArgs a;
-    if (!dz || !y || !stats || !affine || !ws || !dw || !dgamma_dbeta) return fail_msg("syn_conv1d_first_wgrad_bn_lin: null pointer");
-    if (int rc = first_layer_args(a, x, n_clips, l_in, cin, stride, pad, "syn_conv1d_first_wgrad_bn_lin: bad arguments (cin 1 | 2, 64 output channels)")) return rc;
-    if (stride != 5) return fail_msg("syn_conv1d_first_wgrad_bn_lin: stride 5 (the encoder's)");
-    a.DY = dz; a.BY = y; a.bn_stats = stats; a.bn_aff = affine; a.bn_act = act; a.part = ws;
-    hipStream_t s = (hipStream_t)stream;
-    const int groups = first_wgrad_groups(n_clips, a.L_out, 3);      // (64 accumulator + 73 other registers: three waves per SIMD - a fourth workgroup per CU would run in a second round)
-    const float inv_rows = 1.0f / ((float)n_clips * (float)a.L_out);
-    if (cin == 1) {
-        hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin<1>, dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-        hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin_fin<1>, dim3(64), dim3(1024), 0, s, (const float*)ws, groups, affine, inv_rows, dw, dgamma_dbeta);
-    } else {
-        hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin<2>, dim3(groups), dim3(wav::kF1mWaves * 64), 0, s, a);
-        hipLaunchKernelGGL(wav::k_conv_first_wgrad_lin_fin<2>, dim3(64), dim3(1024), 0, s, (const float*)ws, groups, affine, inv_rows, dw, dgamma_dbeta);
-    }
-    return launched("k_conv_first_wgrad_lin launch");
-}
-
-int syn_conv1d_first_wgrad_tail(const float* x, const float* dout, const float* y2, const float* y_short, const float* stats2, const float* affine2,
-                                const float* short_stats, const float* short_affine, const float* dgb2, const float* short_dgb, int32_t act,
-                                int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, float* ws, float* dy2, void* stream) {
-    const FirstTail t = {y2, stats2, affine2, dgb2, dy2};
-    return first_wgrad_impl(x, dout, y_short, short_stats, short_affine, short_dgb, act, n_clips, l_in, cin, stride, pad, ws, nullptr, stream, &t);
-}
-
-int syn_conv1d_first_fwd2(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, const float* w_a, const float* w_b,
-                          float* y_a, float* y_b, float* bn_part_a, float* bn_part_b, void* stream) {
-    wav::FArgs a;
-    if (!w_a || !w_b || !y_a || !y_b || ((bn_part_a == nullptr) != (bn_part_b == nullptr))) return fail_msg("syn_conv1d_first_fwd2: bad arguments");
-    if (int rc = first_layer_args(a, x, n_clips, l_in, cin, stride, pad, "syn_conv1d_first_fwd2: bad arguments (cin 1 | 2, 64 output channels)")) return rc;
-    a.W = w_a; a.W2 = w_b; a.Y = y_a; a.Y2 = y_b; a.part = bn_part_a; a.part2 = bn_part_b;
-    const dim3 grid((a.L_out + wav::kF1Tile - 1) / wav::kF1Tile, n_clips);
-    size_t lds = (size_t)((wav::kF1Tile - 1) * stride + 15) * cin * sizeof(float);
-    if (lds < 2 * 4 * 2 * 64 * sizeof(float)) lds = 2 * 4 * 2 * 64 * sizeof(float);
-    if (cin == 1) hipLaunchKernelGGL(wav::k_conv_first_fwd2<1>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(wav::k_conv_first_fwd2<2>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    return launched("k_conv_first_fwd2 launch");
-}
-
-// backward statistics of a BatchNorm (+ activation) alone - dgamma_dbeta [3][channels] - for a consumer that forms dy itself (syn_conv1d_first_wgrad_bn)
-int syn_bn_bwd_stats(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
-                     int32_t channels, int32_t act, float* ws, float* dgamma_dbeta, void* stream) {
-    if (!dz || !y || !stats || !gamma || !ws || !dgamma_dbeta || rows <= 0 || channels % 4 || 256 % (channels / 4)) return fail_msg("syn_bn_bwd_stats: bad arguments");
-    if (act && !z && !beta) return fail_msg("syn_bn_bwd_stats: without z the activation's sign is recomputed and needs beta");
-    hipStream_t s = (hipStream_t)stream;
-    const int chunks = syn_bn_chunks(rows);
-    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
-    hipLaunchKernelGGL(trn::k_bn_bwd_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgamma_dbeta);
-    return launched("syn_bn_bwd_stats");
-}
-
-// taps of the strided data-gradient GEMM, padded so that taps * cout / 32 is a multiple of the weight ring's 3
-static int dgrad_taps(int stride, int cout) {
-    int kt = (15 + stride - 1) / stride;
-    while ((kt * cout / 32) % 3) ++kt;
-    return kt;
-}
-
-// geometry of one pack: taps (padded), kernel mode, fragments x 64; < 0: not a shape the kernels take
-static int conv_pack_geometry(int cout, int cin, int stride, int transposed, int& kts, int& mode) {
-    if (cout % 16 || cin % 16 || stride < 1 || cout <= 0 || cin <= 0) return -1;
-    int N, C;
-    mode = transposed ? 1 : 0;
-    if (transposed && stride > 1) { mode = 2; kts = dgrad_taps(stride, cout); N = stride * cin; C = cout; }
-    else { kts = (15 + stride - 1) / stride * stride; N = transposed ? cin : cout; C = transposed ? cout : cin; }
-    if ((kts * C) % 32) return -1;
-    return (N / 16) * (kts * C / 32) * 64;
-}
-
-int syn_conv1d_pack_split_many(const syn_conv_pack_req* reqs, int32_t n_reqs, void* stream) {
-    static_assert(SYN_CONV_PACK_MAX == kConvPackMax, "include/syn_hip.h: packs per launch");
-    if (!reqs || n_reqs <= 0 || n_reqs > kConvPackMax) return fail_msg("syn_conv1d_pack_split_many: 1 .. 40 requests");
-    ConvPackJobs j;
-    memset(&j, 0, sizeof(j));
-    int most = 0;
-    for (int i = 0; i < n_reqs; ++i) {
-        const syn_conv_pack_req& r = reqs[i];
-        int kts, mode;
-        const int total = (r.w && r.out_hi && r.out_lo) ? conv_pack_geometry(r.cout, r.cin, r.stride, r.transposed, kts, mode) : -1;
-        if (total < 0) return fail_msg("syn_conv1d_pack_split_many: bad request (as syn_conv1d_pack_split)");
-        j.w[i] = r.w; j.hi[i] = (uint4*)r.out_hi; j.lo[i] = (uint4*)r.out_lo; j.cout[i] = (short)r.cout; j.cin[i] = (short)r.cin;
-        j.kts[i] = (signed char)kts; j.mode[i] = (signed char)mode; j.stride[i] = (signed char)r.stride;
-        most = total > most ? total : most;
-    }
-    hipLaunchKernelGGL(k_conv_pack_split_many, dim3((most + 255) / 256, n_reqs), dim3(256), 0, (hipStream_t)stream, j);
-    return launched("k_conv_pack_split_many launch");
-}
-
-int syn_conv1d_pack_split(const float* w, int32_t cout, int32_t cin, int32_t stride, int32_t transposed, void* out_hi, void* out_lo,
-                          void* stream) {
-    if (!w || !out_hi || !out_lo) return fail_msg("syn_conv1d_pack_split: bad arguments");
-    int kts, mode;
-    const int total = conv_pack_geometry(cout, cin, stride, transposed, kts, mode);
-    if (total < 0) return fail_msg("syn_conv1d_pack_split: channels must be multiples of 16 and taps x channels a multiple of 32");
-    hipLaunchKernelGGL(k_conv_pack_split, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, cout, cin, kts, mode, stride,
-                       (uint4*)out_hi, (uint4*)out_lo);
-    return launched("k_conv_pack_split launch");
-}
-
-int64_t syn_conv1d_pack_bytes(int32_t cout, int32_t cin, int32_t stride, int32_t transposed) {
-    if (cout <= 0 || cin <= 0 || stride < 1) return 0;
-    if (transposed && stride > 1) return (int64_t)stride * cin * dgrad_taps(stride, cout) * cout * 2;
-    const int kts = (15 + stride - 1) / stride * stride;
-    return (int64_t)cout * kts * cin * 2;
-}
-
-// Data gradient of a strided, unpadded Conv1d(k = 15) of the encoder: dx [n][l_in][cin] from dy [n][l_out][cout] - a stride-1
-// convolution over dy whose output rows are stride consecutive positions x cin channels: ONE launch over all stride x cin columns, 64 per
-// workgroup (grid z), a wave 16 channels x 128 / 64 / 32 positions (the decompositions measured in round 5: profiles/r05_ubench_conv_variants.txt).
-static int dgrad_strided_impl(const float* dy, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t cout,
-                              const void* w_hi, const void* w_lo, const float* dy2, const void* w2_hi, const void* w2_lo, float* dx, void* stream) {
-    if (!dy || !w_hi || !w_lo || !dx || n_clips <= 0 || l_in < 15 || stride < 2) return fail_msg("syn_conv1d_train_dgrad_strided: bad arguments");
-    if (dy2 && (!w2_hi || !w2_lo)) return fail_msg("syn_conv1d_train_dgrad_sum: the second gradient needs its fragment sets");
-    const int l_out = (l_in - 15) / stride + 1, kt = dgrad_taps(stride, cout), q_rows = (l_in + stride - 1) / stride, np = stride * cin;
-    if (np % 128) return fail_msg("syn_conv1d_train_dgrad_strided: stride * cin must be a multiple of 128");
-    hipStream_t s = (hipStream_t)stream;
-    wav::TArgs a;
-    a.X = dy; a.x_clip_stride = (long)l_out * cout; a.x_elems = (long)l_out * cout; a.row0 = -(kt - 1); a.L_out = q_rows;
-    a.Whi = (const uint4*)w_hi; a.Wlo = (const uint4*)w_lo; a.bias = nullptr;
-    a.Y = dx; a.y_clip_stride = (long)l_in * cin; a.y_pitch = np; a.y_col0 = 0; a.y_elems = (long)l_in * cin; a.bn_part = nullptr;
-    a.in_aff = nullptr; a.in_act = 0; a.R = nullptr;
-    a.X2 = dy2; a.Whi2 = dy2 ? (const uint4*)w2_hi : nullptr; a.Wlo2 = dy2 ? (const uint4*)w2_lo : nullptr;
-    if (cout == 64 && kt == 3) return launch_conv_train<64, 3, 4, 1, 8, 1>(a, n_clips, s, np);
-    if (cout == 128 && kt == 3) return launch_conv_train<128, 3, 4, 1, 4, 1>(a, n_clips, s, np);
-    if (cout == 256 && kt == 6) return launch_conv_train<256, 6, 4, 1, 2, 1>(a, n_clips, s, np);
-    return fail_msg("syn_conv1d_train_dgrad_strided: (cout, stride) must be (64, 6), (128, 6) or (256, 3)");
-}
-
-// row fragments (16 positions) per tile of the K-split kernel: 3 = 48 positions, 78 KB of LDS, so two workgroups share a CU and
-// one's staging overlaps the other's MFMA phase (4 = 64 positions, 103 KB: one workgroup per CU)
-constexpr int kKsRf = 3;
-// positions per workgroup tile of syn_conv1d_train_fwd's kernel instance (0: not one of the encoder's layers).  The decomposition of every layer
-// class - channels and positions per wave, channel blocks on grid z - is the one that won round 5's comparison (profiles/r05_ubench_conv_variants.txt;
-// the other variants live in the lab notebook, not here): what bounds these kernels is the CU's L1 port (weight fragments), so a wave takes few
-// channels and many positions.
-static int conv_train_tile(int cinp, int stride, int cout, int n_clips, int l_out) {
-    if (cinp == 384 && stride == 6 && cout == 64) return 16 * kKsRf;
-    // (224 positions - two planes of 238 rows x 160 B = 76 KB, two workgroups per CU with the 32-byte row padding; short layers: 128, so that the
-    // launch still fills the chip and the last tile of a clip wastes less)
-    if (cinp == 64 && stride == 1 && cout == 64) return (long)n_clips * ((l_out + 255) / 256) < 2 * device_cus() ? 128 : 224;
-    if (cinp == 128 && stride == 1 && cout == 128) return 64;
-    if (cinp == 256 && stride == 1 && cout == 256) return 32;
-    if (cinp == 384 && stride == 6) return 64;
-    if (cinp == 384 && stride == 3) return 32;
-    return 0;
-}
-
-int32_t syn_conv1d_train_fwd_tiles(int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, int32_t cout) {
-    if (stride < 1) return 0;
-    const int l_out = (l_in + 2 * pad - 15) / stride + 1, mw = l_out > 0 && n_clips > 0 ? conv_train_tile(stride * cin, stride, cout, n_clips, l_out) : 0;
-    return mw ? n_clips * ((l_out + mw - 1) / mw) : 0;
-}
-
-struct ConvDual { const void* w_hi; const void* w_lo; float* y; float* bn_part; };     // a second convolution of the same geometry on the same input
-
-static int conv_train_fwd_impl(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                               const void* w_hi, const void* w_lo, const float* bias, int32_t cout, const float* in_affine, int32_t in_act,
-                               float* y, float* bn_part, void* stream, const float* residual = nullptr, const ConvDual* dual = nullptr) {
-    if (residual && !(stride == 1 && cin * stride != 384)) return fail_msg("syn_conv1d_train_dgrad_sum: the residual rides the stride-1 kernel");
-    if (!x || !w_hi || !w_lo || !y || n_clips <= 0 || l_in <= 0) return fail_msg("syn_conv1d_train_fwd: null pointer / empty batch");
-    if (in_affine && stride != 1) return fail_msg("syn_conv1d_train_fwd_norm: the input affine is for the stride-1 layers (conv2 of a block)");
-    if (stride < 1 || pad < 0 || pad % stride) return fail_msg("syn_conv1d_train_fwd: padding must be a multiple of the stride");
-    const int l_out = (l_in + 2 * pad - 15) / stride + 1;
-    if (l_out <= 0) return fail_msg("syn_conv1d_train_fwd: input shorter than the kernel");
-    wav::TArgs a;
-    a.X = x; a.x_clip_stride = (long)l_in * cin; a.x_elems = (long)l_in * cin; a.row0 = -pad / stride; a.L_out = l_out;
-    a.Whi = (const uint4*)w_hi; a.Wlo = (const uint4*)w_lo; a.bias = bias; a.Y = y; a.y_clip_stride = (long)l_out * cout;
-    a.y_pitch = 0; a.y_col0 = 0; a.y_elems = 0; a.bn_part = bn_part;
-    a.in_aff = in_affine; a.in_act = in_act;
-    a.X2 = nullptr; a.Whi2 = a.Wlo2 = nullptr; a.R = residual;
-    a.WhiB = a.WloB = nullptr; a.YB = nullptr; a.bn_partB = nullptr;
-    if (dual) {
-        if (stride == 1 || bias || !dual->w_hi || !dual->w_lo || !dual->y || ((dual->bn_part == nullptr) != (bn_part == nullptr)))
-            return fail_msg("syn_conv1d_train_fwd_pair: the encoder's strided layers, no bias, both or neither with statistics");
-        a.WhiB = (const uint4*)dual->w_hi; a.WloB = (const uint4*)dual->w_lo; a.YB = dual->y; a.bn_partB = dual->bn_part;
-    }
-    if (bn_part && bias) return fail_msg("syn_conv1d_train_fwd: the statistics are those of the convolution without its bias (pass bias = NULL)");
-    hipStream_t s = (hipStream_t)stream;
-    const int cinp = stride * cin;
-    // (rows of stride * cin floats, ceil(15 / stride) taps; tiles as the eval-mode encoder picks them, halved where two planes
-    // of a 384-channel tile would not fit the LDS)
-    // (short layers: smaller tiles, so that the launch still fills the chip and the last tile of a clip wastes less)
-    if (cinp == 64 && stride == 1 && cout == 64)               // a wave: 32 channels x 112 / 64 positions
-        return conv_train_tile(cinp, stride, cout, n_clips, l_out) > 128 ? launch_conv_train<64, 15, 2, 2, 7, 2>(a, n_clips, s, 64)
-                                                                         : launch_conv_train<64, 15, 2, 2, 4, 2>(a, n_clips, s, 64);
-    if (cinp == 128 && stride == 1 && cout == 128) return launch_conv_train<128, 15, 4, 1, 4, 1>(a, n_clips, s, 128);   // 64 positions x 64 channels per workgroup (z: 2), a wave: 16 channels x 64 positions
-    if (cinp == 256 && stride == 1 && cout == 256) return launch_conv_train<256, 15, 4, 1, 2, 1>(a, n_clips, s, 256);   // 32 positions x 64 channels (z: 4)
-    if (cinp == 384 && stride == 6 && cout == 64) {            // the four waves split K
-        // (a pair goes out as two launches: on this kernel - 48-position tiles, bound by its fixed costs, not by staging - sharing the tile measured
-        //  145 us against 2 x 66)
-        if (int rc = launch_conv_train_ks<384, 3, kKsRf>(a, n_clips, s)) return rc;
-        if (!dual) return 0;
-        a.Whi = a.WhiB; a.Wlo = a.WloB; a.Y = a.YB; a.bn_part = a.bn_partB;
-        return launch_conv_train_ks<384, 3, kKsRf>(a, n_clips, s);
-    }
-    if (cinp == 384 && stride == 6 && cout == 128) return dual ? launch_conv_train<384, 3, 2, 2, 2, 4, true>(a, n_clips, s) : launch_conv_train<384, 3, 2, 2, 2>(a, n_clips, s);   // 64-position tiles
-    if (cinp == 384 && stride == 3 && cout == 256) return dual ? launch_conv_train<384, 5, 4, 1, 2, 1, true>(a, n_clips, s, 256) : launch_conv_train<384, 5, 4, 1, 2, 1>(a, n_clips, s, 256);   // 32 positions x 64 channels (z: 4)
-    return fail_msg("syn_conv1d_train_fwd: not one of the WavEncoder's convolutions (cin x stride -> cout: 64x1->64, 128x1->128, 256x1->256, 64x6->64, 64x6->128, 128x3->256)");
-}
-
-int syn_conv1d_train_fwd(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                         const void* w_hi, const void* w_lo, const float* bias, int32_t cout, float* y, float* bn_part, void* stream) {
-    return conv_train_fwd_impl(x, n_clips, l_in, cin, stride, pad, w_hi, w_lo, bias, cout, nullptr, 0, y, bn_part, stream);
-}
-
-int syn_conv1d_train_fwd_pair(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, int32_t cout,
-                              const void* wa_hi, const void* wa_lo, float* y_a, float* bn_part_a,
-                              const void* wb_hi, const void* wb_lo, float* y_b, float* bn_part_b, void* stream) {
-    const ConvDual d{wb_hi, wb_lo, y_b, bn_part_b};
-    return conv_train_fwd_impl(x, n_clips, l_in, cin, stride, pad, wa_hi, wa_lo, nullptr, cout, nullptr, 0, y_a, bn_part_a, stream, nullptr, &d);
-}
-
-int syn_conv1d_train_fwd_norm(const float* x, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad,
-                              const void* w_hi, const void* w_lo, int32_t cout, const float* in_affine, int32_t in_act, float* y, float* bn_part,
-                              void* stream) {
-    if (!in_affine) return fail_msg("syn_conv1d_train_fwd_norm: in_affine is NULL (use syn_conv1d_train_fwd)");
-    return conv_train_fwd_impl(x, n_clips, l_in, cin, stride, pad, w_hi, w_lo, nullptr, cout, in_affine, in_act, y, bn_part, stream);
-}
-
-int syn_conv1d_train_dgrad_sum(const float* dy, const void* w_hi, const void* w_lo, const float* dy2, const void* w2_hi, const void* w2_lo,
-                               const float* residual, int32_t n_clips, int32_t l_in, int32_t cin, int32_t stride, int32_t pad, int32_t cout, float* dx,
-                               void* stream) {
-    if (stride == 1) {
-        if (dy2) return fail_msg("syn_conv1d_train_dgrad_sum: two gradients are summed for the strided layers (a down-sampling block); stride 1 takes a residual");
-        if (pad != 7) return fail_msg("syn_conv1d_train_dgrad_sum: stride 1 means the padding-7 layers");
-        return conv_train_fwd_impl(dy, n_clips, l_in, cout, 1, 7, w_hi, w_lo, nullptr, cin, nullptr, 0, dx, nullptr, stream, residual);
-    }
-    if (residual || pad != 0) return fail_msg("syn_conv1d_train_dgrad_sum: the strided layers are unpadded and take no residual");
-    return dgrad_strided_impl(dy, n_clips, l_in, cin, stride, cout, w_hi, w_lo, dy2, w2_hi, w2_lo, dx, stream);
 }
 
 // Stage classes reported by syn_denoise_step_profile (index into ms[] / count[]).
@@ -3768,7 +2353,6 @@ int syn_denoise_step_edit(const syn_model* md, const syn_step* st, const syn_edi
     return step_impl(md, st, (hipStream_t)stream, nullptr, 1, 0, 0, ed);
 }
 
-void syn_debug_conv_terms(int mask) { g_conv_terms = mask < 0 ? -1 : (mask & 3); }   /* diagnostics: cross products of the split-operand training convolutions (3 = all) */
 void syn_debug_seq_skew(int units_of_64_cycles) { g_seq_skew = units_of_64_cycles; }
 void syn_debug_seq_step(int step) { g_seq_dbg_step = step; }
 

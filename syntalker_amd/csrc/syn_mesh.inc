@@ -9,6 +9,7 @@
 //
 // The one large product is frames x (3 V) x Kc, Kc = 9 (J - 1) + E (586 for SMPL-X with 100 expression coefficients); v_posed lives in the MFMA's
 // accumulators only, and the per-vertex 4 x 4 that `smplx` materialises (1.2 GB for a 60 s take) never exists.
+namespace {
 namespace mesh {
 
 constexpr int kFrameTile = 32;        // frames per workgroup of k_mesh_vertices (two MFMA row tiles)
@@ -229,31 +230,35 @@ __global__ __launch_bounds__(256) void k_vl_total(const double* __restrict__ col
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0] * (blockIdx.x ? scale_vel : scale_l2);
 }
 
-// ---- entry points -----------------------------------------------------------------------------------------------------------------------------------
 static int64_t packed_floats(int32_t n_verts, int32_t kc) {
     if (n_verts < 1 || kc < 1 || kc > kMaxKc) return -1;
     const int64_t vp = ((int64_t)n_verts + kVertexBlock - 1) / kVertexBlock * kVertexBlock;
     return vp * 3 * kc_padded(kc);
 }
 
-static int pack_dirs(const float* posedirs, const float* exprdirs, int32_t n_verts, int32_t n_pose, int32_t n_expr, float* out, void* stream) {
+}  // namespace mesh
+}  // namespace
+
+// ---- entry points -----------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_mesh_pack_dirs(const float* posedirs, const float* exprdirs, int32_t n_verts, int32_t n_pose, int32_t n_expr, float* out, void* stream) {
     if (!posedirs || !out || (n_expr > 0 && !exprdirs)) return fail_msg("syn_mesh_pack_dirs: null pointer");
-    if (n_verts < 1 || n_pose < 1 || n_expr < 0 || n_pose > kMaxKc || n_expr > kMaxKc || n_pose + n_expr > kMaxKc)
+    if (n_verts < 1 || n_pose < 1 || n_expr < 0 || n_pose > mesh::kMaxKc || n_expr > mesh::kMaxKc || n_pose + n_expr > mesh::kMaxKc)
         return fail_msg("syn_mesh_pack_dirs: no vertices / directions, or more than 1024 directions");
-    const long total = packed_floats(n_verts, n_pose + n_expr);
+    const long total = mesh::packed_floats(n_verts, n_pose + n_expr);
     if ((total + 255) / 256 > 0x7fffffffL) return fail_msg("syn_mesh_pack_dirs: too many elements for one launch");
-    hipLaunchKernelGGL(k_mesh_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, posedirs, exprdirs, (int)n_verts, (int)n_pose,
-                       (int)n_expr, kc_padded(n_pose + n_expr) / kGroup, total, out);
+    hipLaunchKernelGGL(mesh::k_mesh_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, posedirs, exprdirs, (int)n_verts, (int)n_pose,
+                       (int)n_expr, mesh::kc_padded(n_pose + n_expr) / mesh::kGroup, total, out);
     return launched("k_mesh_pack launch");
 }
 
-static int fk_transforms(const int32_t* parents, int32_t n_joints, const float* rest, int32_t n_takes, const float* pose, const float* pose_mean,
-                         const float* joint_dirs, const float* expression, int32_t n_expr, int32_t kc, const float* transl,
-                         const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* feat, float* xforms, float* joints_out,
-                         void* stream) {
-    if (!parents || !rest || !pose || !feat || !xforms || !joints_out) return fail_msg("syn_fk_transforms: null pointer");
+int syn_fk_transforms(const int32_t* parents, int32_t n_joints, const float* rest_joints, int32_t n_takes, const float* pose, const float* pose_mean,
+                      const float* joint_dirs, const float* expression, int32_t n_expr, int32_t kc, const float* transl, const int32_t* take_of_frame,
+                      int32_t frames_per_take, int64_t n_frames, float* feat, float* xforms, float* joints_out, void* stream) {
+    if (!parents || !rest_joints || !pose || !feat || !xforms || !joints_out) return fail_msg("syn_fk_transforms: null pointer");
     if (n_joints < 2 || n_joints > joints::kMaxJ) return fail_msg("syn_fk_transforms: a skinned tree has 2 to 64 joints");
-    if (n_expr < 0 || kc < 9 * (n_joints - 1) + n_expr || kc > kMaxKc)
+    if (n_expr < 0 || kc < 9 * (n_joints - 1) + n_expr || kc > mesh::kMaxKc)
         return fail_msg("syn_fk_transforms: negative expression count, or a row length kc outside 9 (J - 1) + n_expr .. 1024");
     if (n_expr > 0 && (!expression || !joint_dirs)) return fail_msg("syn_fk_transforms: n_expr > 0 needs the expression and joint_dirs");
     if (n_takes < 1 || n_frames < 0) return fail_msg("syn_fk_transforms: no takes / negative frame count");
@@ -264,54 +269,54 @@ static int fk_transforms(const int32_t* parents, int32_t n_joints, const float* 
     if (blocks > 0x7fffffffLL) return fail_msg("syn_fk_transforms: too many frames for one launch");
     joints::FkMesh m = {};
     m.joint_dirs = n_expr > 0 ? joint_dirs : nullptr; m.expr = n_expr > 0 ? expression : nullptr;
-    m.feat = feat; m.xf = xforms; m.E = n_expr; m.Kcp = kc_padded(kc);
+    m.feat = feat; m.xf = xforms; m.E = n_expr; m.Kcp = mesh::kc_padded(kc);
     // without an expression the joints are syn_fk_joints' own, bit for bit: its instance of the kernel writes them (transl folded into the root, as there)
     float* const mesh_joints = n_expr > 0 ? joints_out : nullptr;
-    hipLaunchKernelGGL(joints::k_fk<true>, dim3((unsigned)blocks), dim3(joints::kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest,
+    hipLaunchKernelGGL(joints::k_fk<true>, dim3((unsigned)blocks), dim3(joints::kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints, rest_joints,
                        (int)n_takes, pose, 0, transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, mesh_joints, pose_mean, m);
     if (n_expr == 0) {
         if (int rc = launched("k_fk launch (mesh outputs)")) return rc;
         hipLaunchKernelGGL(joints::k_fk<false>, dim3((unsigned)blocks), dim3(joints::kFkThreads), 0, (hipStream_t)stream, (const int*)parents, (int)n_joints,
-                           rest, (int)n_takes, pose, 0, transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, joints_out, pose_mean,
+                           rest_joints, (int)n_takes, pose, 0, transl, (const int*)take_of_frame, (int)frames_per_take, (long)n_frames, joints_out, pose_mean,
                            joints::FkMesh{});
     }
     return launched("k_fk launch (mesh outputs)");
 }
 
-static int vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, const float* feat, const float* xforms, int32_t n_joints, const float* v_shaped,
-                    int32_t n_takes, const int32_t* skin_index, const float* skin_weight, int32_t width, const float* transl,
-                    const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* out, void* stream) {
-    if (!dirs_packed || !feat || !xforms || !v_shaped || !skin_index || !skin_weight || !out) return fail_msg("syn_mesh_vertices: null pointer");
+int syn_mesh_vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, const float* feat, const float* xforms, int32_t n_joints,
+                      const float* v_shaped, int32_t n_takes, const int32_t* skin_index, const float* skin_weight, int32_t width, const float* transl,
+                      const int32_t* take_of_frame, int32_t frames_per_take, int64_t n_frames, float* vertices_out, void* stream) {
+    if (!dirs_packed || !feat || !xforms || !v_shaped || !skin_index || !skin_weight || !vertices_out) return fail_msg("syn_mesh_vertices: null pointer");
     if (n_joints < 1 || n_joints > joints::kMaxJ) return fail_msg("syn_mesh_vertices: 1 to 64 joints");
     if (width < 1 || width > n_joints) return fail_msg("syn_mesh_vertices: the weight lists are 1 to n_joints entries wide");
-    if (n_verts < 1 || kc < 1 || kc > kMaxKc) return fail_msg("syn_mesh_vertices: no vertices, or a contraction length outside 1 .. 1024");
+    if (n_verts < 1 || kc < 1 || kc > mesh::kMaxKc) return fail_msg("syn_mesh_vertices: no vertices, or a contraction length outside 1 .. 1024");
     if (n_takes < 1 || n_frames < 0) return fail_msg("syn_mesh_vertices: no takes / negative frame count");
     if (!take_of_frame && frames_per_take < 1) return fail_msg("syn_mesh_vertices: give a frame-to-take index or the frames per take");
     if (!take_of_frame && n_frames > (int64_t)n_takes * frames_per_take) return fail_msg("syn_mesh_vertices: more frames than n_takes x frames_per_take");
     if (((uintptr_t)dirs_packed | (uintptr_t)feat | (uintptr_t)xforms) & 15) return fail_msg("syn_mesh_vertices: dirs_packed, feat and xforms must be 16-byte aligned");
     if (n_frames == 0) return 0;
-    VertArgs a = {};
+    mesh::VertArgs a = {};
     a.dirs = dirs_packed; a.feat = feat; a.xf = xforms; a.v_shaped = v_shaped; a.skin_idx = (const int*)skin_index; a.skin_w = skin_weight;
-    a.transl = transl; a.take_of_frame = (const int*)take_of_frame; a.out = out; a.N = (long)n_frames;
-    a.V = n_verts; a.Kcp = kc_padded(kc); a.G = a.Kcp / kGroup; a.J = n_joints; a.W = width; a.n_takes = n_takes; a.frames_per_take = frames_per_take;
-    const int64_t ftiles = (n_frames + kFrameTile - 1) / kFrameTile, vblocks = ((int64_t)n_verts + kVertexBlock - 1) / kVertexBlock;
+    a.transl = transl; a.take_of_frame = (const int*)take_of_frame; a.out = vertices_out; a.N = (long)n_frames;
+    a.V = n_verts; a.Kcp = mesh::kc_padded(kc); a.G = a.Kcp / mesh::kGroup; a.J = n_joints; a.W = width; a.n_takes = n_takes; a.frames_per_take = frames_per_take;
+    const int64_t ftiles = (n_frames + mesh::kFrameTile - 1) / mesh::kFrameTile, vblocks = ((int64_t)n_verts + mesh::kVertexBlock - 1) / mesh::kVertexBlock;
     if (ftiles * vblocks > 0x3fffffffLL) return fail_msg("syn_mesh_vertices: too many frame tiles x vertex blocks for one launch");
-    a.ftiles = (int)ftiles; a.total = (int)(ftiles * vblocks); a.stride = lds_stride(a.Kcp);
-    const int feat_floats = kFrameTile * a.stride, xf_floats = 16 * n_joints * 12;        // (the epilogue stages one row tile of transforms at a time)
+    a.ftiles = (int)ftiles; a.total = (int)(ftiles * vblocks); a.stride = mesh::lds_stride(a.Kcp);
+    const int feat_floats = mesh::kFrameTile * a.stride, xf_floats = 16 * n_joints * 12;        // (the epilogue stages one row tile of transforms at a time)
     const int lds = 4 * (feat_floats > xf_floats ? feat_floats : xf_floats);
     static OncePerDevice once;
-    if (once.first()) allow_lds(k_mesh_vertices, 4 * kFrameTile * lds_stride(kMaxKc));
-    const unsigned grid = (unsigned)((a.total + kXcds - 1) / kXcds * kXcds);
-    hipLaunchKernelGGL(k_mesh_vertices, dim3(grid), dim3(256), (size_t)lds, (hipStream_t)stream, a);
+    if (once.first()) allow_lds(mesh::k_mesh_vertices, 4 * mesh::kFrameTile * mesh::lds_stride(mesh::kMaxKc));
+    const unsigned grid = (unsigned)((a.total + mesh::kXcds - 1) / mesh::kXcds * mesh::kXcds);
+    hipLaunchKernelGGL(mesh::k_mesh_vertices, dim3(grid), dim3(256), (size_t)lds, (hipStream_t)stream, a);
     return launched("k_mesh_vertices launch");
 }
 
-static int64_t losses_workspace(int64_t n, int32_t channels) {
+int64_t syn_vertex_losses_workspace_bytes(int64_t n, int32_t channels) {
     if (n < 1 || channels < 1) return -1;
     return 2 * (((n + joints::kL1Rows - 1) / joints::kL1Rows) * channels + (int64_t)channels) * (int64_t)sizeof(double);
 }
 
-static int losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
+int syn_vertex_losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream) {
     if (!rec || !tar || !workspace || !out) return fail_msg("syn_vertex_losses: null pointer");
     if (n < 1 || channels < 1) return fail_msg("syn_vertex_losses: empty input");
     if (((uintptr_t)workspace | (uintptr_t)out) & 7) return fail_msg("syn_vertex_losses: workspace and out must be 8-byte aligned");
@@ -322,11 +327,11 @@ static int losses(const float* rec, const float* tar, int64_t n, int32_t channel
     double* part = (double*)workspace;
     double* col = part + 2 * total;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_vl_chunks, dim3((unsigned)grid), dim3(256), 0, s, rec, tar, (long)n, (int)channels, part);
+    hipLaunchKernelGGL(mesh::k_vl_chunks, dim3((unsigned)grid), dim3(256), 0, s, rec, tar, (long)n, (int)channels, part);
     hipLaunchKernelGGL(joints::k_l1_columns, dim3((unsigned)((channels + 255) / 256), 2u), dim3(256), 0, s, (const double*)part, chunks, (int)channels, 1.0, col);
-    hipLaunchKernelGGL(k_vl_total, dim3(2), dim3(256), 0, s, (const double*)col, (int)channels, 1.0 / ((double)n * channels),
+    hipLaunchKernelGGL(mesh::k_vl_total, dim3(2), dim3(256), 0, s, (const double*)col, (int)channels, 1.0 / ((double)n * channels),
                        1.0 / ((double)(n - 1) * channels), out);      // (n = 1: no differences, 0 / 0 = NaN, torch's mean of an empty tensor)
     return launched("k_vertex_losses launches");
 }
 
-}  // namespace mesh
+}  // extern "C"

@@ -6,6 +6,7 @@
 // NEXT step.  Everything is per element and x_t, x0_hat, the ring and H share one element order, so token-major and fragment-order latents
 // take the same kernel.  The row of the table (r, 1 / m, the next step's weights by ring slot, the slot to overwrite) is picked by the
 // device-side step counter that k_step_advance maintains: a captured graph replays for every step.
+namespace {
 namespace plms {
 
 // per element: reads x_t and x0_hat (8 B) and up to two ring slots (8 B), writes a ring slot (4 B, when the estimate is read again) and H (4 B):
@@ -49,17 +50,18 @@ __global__ __launch_bounds__(256) void k_plms_update(const syn_plms_row* __restr
     }
 }
 
-static int update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
-                  float* ring, float* h, int64_t n, void* stream) {
+}  // namespace plms
+}  // namespace
+
+extern "C" int syn_plms_update(const syn_plms_row* table, int32_t n_rows, const int32_t* counter, int32_t back, const float* x_t, const float* pred_x0,
+                               float* ring, float* h, int64_t n, void* stream) {
     if (!table || n_rows <= 0 || !counter || back < 0 || !x_t || !pred_x0 || !ring || !h || n <= 0 || n % 4)
         return fail_msg("syn_plms_update: null pointer, empty table, negative `back`, or n not a positive multiple of 4");
     if (((uintptr_t)x_t | (uintptr_t)pred_x0 | (uintptr_t)ring | (uintptr_t)h) & 15)
         return fail_msg("syn_plms_update: x_t, pred_x0, ring and h must be 16-byte aligned");
     const long n4 = (long)(n / 4);
     const long want = (n4 + 255) / 256, cap = (long)device_cus() * 8;       // a grid sized from the CU count, grid-stride over the rest
-    hipLaunchKernelGGL(k_plms_update, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, (hipStream_t)stream, table, (int)n_rows,
+    hipLaunchKernelGGL(plms::k_plms_update, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, (hipStream_t)stream, table, (int)n_rows,
                        (const int*)counter, (int)back, (const f32x4*)x_t, (const f32x4*)pred_x0, (f32x4*)ring, (f32x4*)h, n4);
     return launched("k_plms_update launch");
 }
-
-}  // namespace plms

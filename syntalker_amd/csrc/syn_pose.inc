@@ -4,6 +4,7 @@
 // launches each - here one thread does one joint.  Elementwise fp32 work (36 B per joint): HBM-bound by construction, nothing to tile.
 // The arithmetic follows the reference's helpers operation for operation (same small-angle series, same sqrt-of-positive-part + copysign quaternion),
 // so that the two agree to fp32 rounding away from the representation's own singularities.
+namespace {
 namespace pose {
 
 // axis_angle_to_quaternion (rotation_conversions.py:448-477) -> quaternion_to_matrix (:36-64) -> matrix_to_rotation_6d (:535-550)
@@ -59,3 +60,23 @@ __global__ __launch_bounds__(256) void k_rot6d_to_aa(const float* __restrict__ d
 }
 
 }  // namespace pose
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_axis_angle_to_rot6d(const float* axis_angle, int64_t n_joints, float* rot6d, void* stream) {
+    if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_axis_angle_to_rot6d: null pointer / negative count");
+    if (n_joints == 0) return 0;
+    hipLaunchKernelGGL(pose::k_aa_to_rot6d, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, axis_angle, (long)n_joints, rot6d);
+    return launched("k_aa_to_rot6d launch");
+}
+
+int syn_rot6d_to_axis_angle(const float* rot6d, int64_t n_joints, float* axis_angle, void* stream) {
+    if (!axis_angle || !rot6d || n_joints < 0) return fail_msg("syn_rot6d_to_axis_angle: null pointer / negative count");
+    if (n_joints == 0) return 0;
+    hipLaunchKernelGGL(pose::k_rot6d_to_aa, dim3((unsigned)((n_joints + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rot6d, (long)n_joints, axis_angle);
+    return launched("k_rot6d_to_aa launch");
+}
+
+}  // extern "C"

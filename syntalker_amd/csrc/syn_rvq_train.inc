@@ -1,5 +1,5 @@
 // syn_rvq_train.inc — training the body-part RVQ-VAEs (reference rvq_beatx_train.py over models/vq/{model,encdec,resnet,residual_vq,
-// quantizer}.py in train mode; DESIGN.md §16).  Included by syn_kernels.hip behind syn_rvq.inc; entry points syn_vq_train_*.
+// quantizer}.py in train mode; DESIGN.md §16).  Included by syn_kernels.hip behind syn_rvq.inc; entry points syn_vq_train_* at the end.
 //
 // The convolutions of the step run on the eval path's kernel, rvq::k_conv1d, untouched (syn_vq_conv1d): the forward with the bf16 input of
 // every convolution kept, the data gradients as the same convolution over tap-flipped, transposed weights (k_pack_jobs below writes both
@@ -14,6 +14,7 @@
 //   k_recons / k_scalars    the reconstruction loss, its gradient and the four numbers a step reports
 // Everything is a fixed-order sum: no floating-point atomics, two runs on the same inputs are bit-equal.
 
+namespace {
 namespace rvqt {
 
 using rvq::kCodes;
@@ -494,3 +495,119 @@ __global__ __launch_bounds__(512) void k_scalars(const float* __restrict__ part,
 }
 
 }  // namespace rvqt
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_vq_train_pack(const void* jobs_dev, int32_t n_jobs, int32_t max_units, void* stream) {
+    if (!jobs_dev || n_jobs <= 0 || max_units <= 0) return fail_msg("syn_vq_train_pack: bad arguments");
+    hipLaunchKernelGGL(rvqt::k_pack_jobs, dim3((max_units + 255) / 256, n_jobs), dim3(256), 0, (hipStream_t)stream, (const rvqt::PackJob*)jobs_dev);
+    return launched("k_pack_jobs launch");
+}
+
+int syn_vq_train_cast(const float* x, int64_t rows, int32_t dim, int32_t dim_padded, void* out_bf16, void* out_lo_bf16, void* stream) {
+    if (!x || !out_bf16 || rows <= 0 || dim <= 0 || dim_padded < dim) return fail_msg("syn_vq_train_cast: bad arguments");
+    const long n = (long)rows * dim_padded;
+    hipLaunchKernelGGL(rvqt::k_cast_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (__bf16*)out_bf16, (__bf16*)out_lo_bf16, n, dim, dim_padded);
+    return launched("k_cast_pad launch");
+}
+
+int syn_vq_train_ew(const float* v, const float* resid, const void* relu_src_bf16, const uint8_t* keep, float scale_v, float scale_resid,
+                    float* out_f32, void* out_bf16, void* out_lo_bf16, int32_t lo_relu, int64_t n, void* stream) {
+    if (!v || (!out_f32 && !out_bf16 && !out_lo_bf16) || n <= 0 || n % 4) return fail_msg("syn_vq_train_ew: bad arguments (n % 4 == 0)");
+    hipLaunchKernelGGL(rvqt::k_ew, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, resid, (const __bf16*)relu_src_bf16, keep,
+                       scale_v, scale_resid, out_f32, (__bf16*)out_bf16, (__bf16*)out_lo_bf16, lo_relu, (long)(n / 4));
+    return launched("k_ew launch");
+}
+
+int syn_vq_train_pairsum(const float* du, float* out, int64_t rows_out, int32_t channels, void* stream) {
+    if (!du || !out || rows_out <= 0 || channels <= 0 || channels % 4) return fail_msg("syn_vq_train_pairsum: bad arguments (channels % 4 == 0)");
+    const long n4 = (long)rows_out * (channels / 4);
+    hipLaunchKernelGGL(rvqt::k_pairsum, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, du, out, n4, channels / 4);
+    return launched("k_pairsum launch");
+}
+
+int syn_vq_train_stuff(const void* dy_bf16, void* out_bf16, int64_t rows_in, int32_t channels, void* stream) {
+    if (!dy_bf16 || !out_bf16 || rows_in <= 0 || channels <= 0 || channels % 8) return fail_msg("syn_vq_train_stuff: bad arguments (channels % 8 == 0)");
+    const long n8 = (long)rows_in * (channels / 8);
+    hipLaunchKernelGGL(rvqt::k_stuff, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)dy_bf16, (uint4*)out_bf16, n8, channels / 8);
+    return launched("k_stuff launch");
+}
+
+int syn_vq_train_wgrad(const void* dy_bf16, int32_t ldy, const void* x_bf16, int32_t ldx, float* dw, float* db, int32_t clips, int32_t t_in,
+                       int32_t t_out, int32_t cout, int32_t cin, int32_t taps, int32_t stride, int32_t dil, int32_t pad, int32_t up, int32_t relu_in,
+                       void* stream) {
+    if (!dy_bf16 || !x_bf16 || !dw || clips <= 0 || t_in <= 0 || t_out <= 0 || cout <= 0 || cin <= 0 || taps <= 0 || stride <= 0 || dil <= 0 || pad < 0 ||
+        up < 0 || up > 1 || ldy < cout || ldx < cin || ldy % 8 || ldx % 8 || (int64_t)clips * t_out >= (1ll << 30) || (int64_t)clips * t_in >= (1ll << 30))
+        return fail_msg("syn_vq_train_wgrad: bad arguments (row pitches: multiples of 8 channels that hold cout / cin)");
+    rvqt::WgArgs a;
+    a.DY = (const __bf16*)dy_bf16; a.X = (const __bf16*)x_bf16; a.dW = dw; a.ldy = ldy; a.ldx = ldx; a.clips = clips; a.t_in = t_in; a.t_out = t_out;
+    a.cout = cout; a.cin = cin; a.taps = taps; a.stride = stride; a.dil = dil; a.pad = pad; a.up = up; a.relu_in = relu_in;
+    hipLaunchKernelGGL(rvqt::k_wgrad, dim3((cout + 63) / 64, (cin + 63) / 64, taps), dim3(256), 0, (hipStream_t)stream, a);
+    int rc = launched("k_wgrad launch");
+    if (rc || !db) return rc;
+    hipLaunchKernelGGL(rvqt::k_colsum, dim3((cout + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const __bf16*)dy_bf16, ldy, clips * t_out, cout, db);
+    return launched("k_colsum launch");
+}
+
+int syn_vq_train_codebook_prep(const float* codebook, float* codebook_t, float* code_sq, void* stream) {
+    if (!codebook || !codebook_t || !code_sq) return fail_msg("syn_vq_train_codebook_prep: bad arguments");
+    hipLaunchKernelGGL(rvqt::k_cb_t, dim3(rvq::kCodes / 32, rvq::kDim / 32), dim3(256), 0, (hipStream_t)stream, codebook, codebook_t);
+    hipLaunchKernelGGL(rvqt::k_cb_sq, dim3(rvq::kCodes / 256), dim3(256), 0, (hipStream_t)stream, (const float*)codebook_t, code_sq);
+    return launched("k_cb_t / k_cb_sq launch");
+}
+
+int syn_vq_train_tile(const float* x, int32_t rows, const float* noise, float* codebook, float* code_sum, float* code_count, void* stream) {
+    if (!x || rows <= 0 || (rows < rvq::kCodes && !noise) || !codebook || !code_sum || !code_count) return fail_msg("syn_vq_train_tile: bad arguments (fewer rows than codes need the noise)");
+    hipLaunchKernelGGL(rvqt::k_tile_init, dim3(rvq::kCodes), dim3(256), 0, (hipStream_t)stream, x, rows, noise, (float)(0.01 / sqrt((double)rvq::kDim)), codebook, code_sum, code_count);
+    return launched("k_tile_init launch");
+}
+
+int syn_vq_train_quantize(const float* x_in, const float* codebook, const float* codebook_t, const float* code_sq, const float* gumbel, float temperature,
+                          float* x_out, float* q_acc, void* q_bf16, float* resid_sum, int32_t* idx, float* sqerr, int32_t layer, int32_t first, int32_t rows,
+                          void* stream) {
+    if (!x_in || !codebook || !codebook_t || !code_sq || !x_out || x_out == x_in || !q_acc || !resid_sum || !idx || !sqerr || layer < 0 || layer >= rvq::kQ ||
+        rows <= 0 || (gumbel && !(temperature > 0.f)))
+        return fail_msg("syn_vq_train_quantize: bad arguments");
+    rvqt::QtArgs a;
+    a.Xin = x_in; a.CB = codebook; a.CBT = codebook_t; a.CC = code_sq; a.G = gumbel; a.temperature = temperature; a.Xout = x_out; a.Qacc = q_acc;
+    a.Qb = (__bf16*)q_bf16; a.Rsum = resid_sum; a.idx = idx; a.sqerr = sqerr; a.layer = layer; a.first = first; a.rows = rows;
+    const int groups = syn_vq_quantize_groups(rows);
+    if (rvq::q_rows(rows) == 4) hipLaunchKernelGGL(rvqt::k_quantize_train<4>, dim3(groups), dim3(256), 0, (hipStream_t)stream, a);
+    else                        hipLaunchKernelGGL(rvqt::k_quantize_train<16>, dim3(groups), dim3(256), 0, (hipStream_t)stream, a);
+    return launched("k_quantize_train launch");
+}
+
+int syn_vq_train_codebook_update(const float* x_in, const int32_t* idx, int32_t layer, int32_t rows, const float* noise, float mu, float one_minus_mu,
+                                 float* codebook, float* code_sum, float* code_count, float* batch_count, void* stream) {
+    if (!x_in || !idx || layer < 0 || layer >= rvq::kQ || rows <= 0 || (rows < rvq::kCodes && !noise) || !codebook || !code_sum || !code_count || !batch_count)
+        return fail_msg("syn_vq_train_codebook_update: bad arguments (fewer rows than codes need the noise)");
+    hipLaunchKernelGGL(rvqt::k_code_update, dim3(rvq::kCodes), dim3(256), 0, (hipStream_t)stream, x_in, idx, layer, rows, noise,
+                       (float)(0.01 / sqrt((double)rvq::kDim)), mu, one_minus_mu, codebook, code_sum, code_count, batch_count);
+    return launched("k_code_update launch");
+}
+
+int32_t syn_vq_train_loss_parts(int64_t rows, int32_t dim_padded) {
+    if (rows <= 0 || dim_padded <= 0) return -1;
+    return (int32_t)((rows * dim_padded + 256 * rvqt::kLossPer - 1) / (256 * rvqt::kLossPer));
+}
+
+int syn_vq_train_loss(const float* rec, const float* gt, int64_t rows, int32_t dim, int32_t dim_padded, int32_t kind, void* d_rec_bf16, float* parts,
+                      void* stream) {
+    if (!rec || !gt || !d_rec_bf16 || !parts || rows <= 0 || dim <= 0 || dim_padded < dim || kind < 0 || kind > 2) return fail_msg("syn_vq_train_loss: bad arguments");
+    hipLaunchKernelGGL(rvqt::k_recons, dim3(syn_vq_train_loss_parts(rows, dim_padded)), dim3(256), 0, (hipStream_t)stream, rec, gt, (long)rows * dim_padded, dim,
+                       dim_padded, kind, (float)(1.0 / ((double)rows * dim)), (__bf16*)d_rec_bf16, parts);
+    return launched("k_recons launch");
+}
+
+int syn_vq_train_scalars(const float* parts, int32_t n_parts, int64_t count, const float* sqerr, int32_t groups, const float* batch_count, int32_t n_active,
+                         int32_t rows, float commit_weight, float* out4, void* stream) {
+    if (!parts || n_parts <= 0 || count <= 0 || !sqerr || groups <= 0 || !batch_count || n_active < 1 || n_active > rvq::kQ || rows <= 0 || !out4)
+        return fail_msg("syn_vq_train_scalars: bad arguments");
+    hipLaunchKernelGGL(rvqt::k_scalars, dim3(1), dim3(512), 0, (hipStream_t)stream, parts, n_parts, (float)(1.0 / (double)count), sqerr, groups, batch_count,
+                       n_active, rows, commit_weight, out4);
+    return launched("k_scalars launch");
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // syn_seq.inc — k_seq: the whole denoising step, one WAVE per sequence, four sequences per workgroup (large batches).
-// (Included inside syn_kernels.hip's anonymous namespace.)
+// (Included by syn_kernels.hip; its entry points - the step and the fragment-order converters - are there.)
 //
 // Why a second whole-step kernel.  k_stack keeps 64 rows (2 sequences) per CU: its LayerNorm output (64 KB) and the
 // q/k/v / hidden staging (64 KB) fill the LDS, and every workgroup pulls the 38 MB weight set through its CU's 64 B/clk
@@ -29,6 +29,7 @@
 //
 // Reference semantics: models/denoiser.py:132-196 (hoisted + folded, SURVEY 8 a17-a20), timm_transformer/transformer.py:
 // 83-104,145-151,195-198, gaussian_diffusion.py:505-557 / :741-791 for the update.
+namespace {
 namespace seq {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -951,3 +952,4 @@ __global__ __launch_bounds__(kThreads) void k_mfma_rate(float* __restrict__ out,
 }
 
 }  // namespace seq
+}  // namespace

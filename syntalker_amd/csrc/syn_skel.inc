@@ -7,6 +7,7 @@
 // GroupNorm needs the whole take: layer i writes its pre-norm r | s and, per 16-frame tile and group, the fp64 sum and sum of squares;
 // layer i + 1 reduces those in tile order, then applies the affine, the shortcut add, the pooling and tanh while staging its window.
 // k_skel_out does the same for the last layer and writes the embedding.  No atomics: bitwise reproducible, clips independent.
+namespace {
 namespace skel {
 
 constexpr int kTile = 16;                        // output frames per workgroup (the MFMA's M)
@@ -189,17 +190,23 @@ static inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 static inline int cin_pad(int cin) { return (int)round_up(cin, 4); }
 static inline int lds_stride(int cin_p) { return cin_p + (int)((34 - cin_p % 32) % 32); }     // = 2 mod 32: the 16 x 4 A reads hit 64 banks
 
-static int pack_weight(const float* w, const float* mask, const float* ws, const float* ms, int32_t cout, int32_t cin, const int32_t* chunk_off,
-                       const int32_t* chunk_k, float* out, void* stream) {
-    if (!w || !mask || !ws || !ms || !chunk_off || !chunk_k || !out || cout < 1 || cout > kMaxC || cin < 1 || cin > kMaxC)
+}  // namespace skel
+}  // namespace
+
+extern "C" {
+
+int syn_skel_pack_weight(const float* w, const float* mask, const float* ws, const float* ms, int32_t cout, int32_t cin, const int32_t* chunk_off,
+                         const int32_t* chunk_k, float* out, void* stream) {
+    if (!w || !mask || !ws || !ms || !chunk_off || !chunk_k || !out || cout < 1 || cout > skel::kMaxC || cin < 1 || cin > skel::kMaxC)
         return fail_msg("syn_skel_pack_weight: null pointer, or channels outside 1 .. SYN_SKEL_MAX_C");
-    const int cout_p = (int)round_up(cout, kTile);
-    hipLaunchKernelGGL(k_skel_pack, dim3((unsigned)(2 * cout_p / kTile)), dim3(64), 0, (hipStream_t)stream, w, mask, ws, ms, (int)cout, (int)cin,
+    const int cout_p = (int)skel::round_up(cout, skel::kTile);
+    hipLaunchKernelGGL(skel::k_skel_pack, dim3((unsigned)(2 * cout_p / skel::kTile)), dim3(64), 0, (hipStream_t)stream, w, mask, ws, ms, (int)cout, (int)cin,
                        cout_p, chunk_off, chunk_k, out);
     return launched("k_skel_pack launch");
 }
 
-static int encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
+int syn_skel_encode(const syn_skel_model* m, const float* x, int32_t n_clips, int32_t n_frames, void* workspace, float* out, void* stream) {
+    using namespace skel;
     if (!m || !x || !workspace || !out) return fail_msg("syn_skel_encode: null pointer");
     if (n_clips < 1 || n_clips > SYN_SKEL_MAX_CLIPS || n_frames < 16 || n_frames % 16 || n_frames > (1 << 24))
         return fail_msg("syn_skel_encode: n_clips outside 1 .. SYN_SKEL_MAX_CLIPS or n_frames not a positive multiple of 16 (at most 2^24)");
@@ -238,4 +245,5 @@ static int encode(const syn_skel_model* m, const float* x, int32_t n_clips, int3
     hipLaunchKernelGGL(k_skel_out, dim3((unsigned)((long)n_clips * src.tiles)), dim3(256), 0, st, src, src.tiles, out);
     return launched("k_skel_out launch");
 }
-}  // namespace skel
+
+}  // extern "C"

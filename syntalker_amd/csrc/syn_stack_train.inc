@@ -1,6 +1,6 @@
 // syn_stack_train.inc — the 8 transformer blocks of the TRAINING forward as one persistent kernel (round 5; SURVEY.md §8 a10 / a19;
 // reference models/timm_transformer/transformer.py:154-198 Block, :83-104 Attention, :145-151 Mlp, :21-38 DropPath).
-// Included by syn_kernels.hip behind k_stack, whose tile-split mode it is built on.
+// Included by syn_kernels.hip behind k_stack, whose tile-split mode it is built on; entry points syn_train_stack_* at the end.
 //
 // Why.  Issued as one launch per operation the forward of the blocks is 56 launches of 6-10 us for 38 GFLOP (profiles/r04_train_step_split.txt:
 // 0.55 ms, every launch at its latency floor).  k_stack already runs this arithmetic for sampling as ONE launch: a 32-row tile (one sequence)
@@ -13,6 +13,7 @@
 //     qkv and the fc1 pre-activation (fp32), and the four operand transposes of the weight-gradient GEMMs as packed MFMA fragments
 //     (LayerNorm outputs, attention output, GELU output: gathered out of the LDS tiles the forward GEMMs read).
 // Arithmetic = k_stack's (bf16 operands incl. q / k / v / p, fp32 accumulate, fp32 residual / LayerNorm / softmax).
+namespace {
 namespace stk {
 
 constexpr int kTrainLds = 72 * 1024 + 64 * 1024;       // k_stack<32>'s tiles (68 KB, rounded) + the branch input's fp32 copy
@@ -838,3 +839,107 @@ __global__ __launch_bounds__(kThreads) void k_stack_train_bwd(const TArgsB a) {
 constexpr int kTrainBwdLds = 32 * 1024 + 32768 + 3 * 128 * 72 + 512 + 32 * 16 * 4 + 64;
 
 }  // namespace stk
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int syn_train_stack_fwd(const syn_train_stack* t, void* stream) {
+    if (!t || !t->h_in || !t->h_out || !t->sync || !t->xch || t->n_seq < 1 || t->n_seq > 64) return fail_msg("syn_train_stack_fwd: 1 .. 64 sequences, non-null pointers");
+    if (!latency_path_ok()) return fail_msg("syn_train_stack_fwd: needs a 256-CU (8 XCD x 32) device");
+    stk::TArgsS a;
+    memset(&a, 0, sizeof(a));
+    a.H = t->h_in; a.Hout = t->h_out; a.dp = t->drop_path; a.M = 32 * t->n_seq; a.tiles = t->n_seq; a.sync = t->sync; a.xch = t->xch; a.flags = t->reserved;
+    for (int l = 0; l < SYN_LAYERS; ++l) {
+        const syn_layer& L = t->layer[l];
+        const syn_train_block_save& S = t->save[l];
+        if (!L.ln1_g || !L.ln1_b || !L.w_qkv || !L.w_proj || !L.b_proj || !L.ln2_g || !L.ln2_b || !L.w_fc1 || !L.b_fc1 || !L.w_fc2 || !L.b_fc2)
+            return fail_msg("syn_train_stack_fwd: a block's weights are incomplete");
+        if (!S.h_attn || !S.mean_attn || !S.rstd_attn || !S.qkv || !S.xt_ln1 || !S.xt_attn || !S.h_mlp || !S.mean_mlp || !S.rstd_mlp || !S.pre || !S.xt_ln2 || !S.xt_gelu)
+            return fail_msg("syn_train_stack_fwd: a block's saved tensors are incomplete");
+        a.layer[l] = L;
+        stk::TrainSave& d = a.save[l];
+        d.hA = S.h_attn; d.meanA = S.mean_attn; d.rstdA = S.rstd_attn; d.qkv = S.qkv; d.xt_ln1 = (uint4*)S.xt_ln1; d.xt_o = (uint4*)S.xt_attn;
+        d.hM = S.h_mlp; d.meanM = S.mean_mlp; d.rstdM = S.rstd_mlp; d.pre = S.pre; d.xt_ln2 = (uint4*)S.xt_ln2; d.xt_a = (uint4*)S.xt_gelu;
+    }
+    static OncePerDevice once;
+    if (once.first()) { allow_lds(stk::k_stack_train, stk::kTrainLds); }
+    const int grid = lat::kGroups * 4 * ((t->n_seq + lat::kGroups - 1) / lat::kGroups);
+    hipLaunchKernelGGL(stk::k_stack_train, dim3(grid), dim3(kThreads), stk::kTrainLds, (hipStream_t)stream, a);
+    return launched("k_stack_train launch");
+}
+
+int syn_train_stack_bwd(const syn_train_stack_grad* t, void* stream) {
+    if (!t || !t->fwd || !t->dh_out || !t->dh_in || !t->stash) return fail_msg("syn_train_stack_bwd: null argument");
+    const syn_train_stack& f = *t->fwd;
+    if (f.n_seq < 1 || f.n_seq > 64 || !f.sync || !f.xch) return fail_msg("syn_train_stack_bwd: 1 .. 64 sequences, the forward's sync / xch");
+    if (!latency_path_ok()) return fail_msg("syn_train_stack_bwd: needs a 256-CU (8 XCD x 32) device");
+    stk::TArgsB a;
+    memset(&a, 0, sizeof(a));
+    a.dH = t->dh_out; a.dHin = t->dh_in; a.dp = f.drop_path; a.M = 32 * f.n_seq; a.tiles = f.n_seq; a.sync = f.sync; a.xch = f.xch; a.stash = t->stash;
+    a.l_first = t->first_block; a.l_last = t->last_block; a.flags = f.reserved;
+    if (a.l_first < a.l_last || a.l_last < 0 || a.l_first >= SYN_LAYERS) return fail_msg("syn_train_stack_bwd: blocks are walked downwards: SYN_LAYERS > first_block >= last_block >= 0");
+    for (int l = 0; l < SYN_LAYERS; ++l) {
+        const syn_layer& L = t->layer_t[l];
+        const syn_train_block_save& S = f.save[l];
+        const syn_train_block_grad& G = t->grad[l];
+        if (!L.ln1_g || !L.w_qkv || !L.w_proj || !L.ln2_g || !L.w_fc1 || !L.w_fc2) return fail_msg("syn_train_stack_bwd: a block's transposed weights / LayerNorm gains are incomplete");
+        if (!G.dyt_fc2 || !G.dyt_fc1 || !G.dyt_proj || !G.dyt_qkv || !G.part) return fail_msg("syn_train_stack_bwd: a block's outputs are incomplete");
+        a.layer[l] = L;
+        stk::TrainSave& d = a.save[l];
+        d.hA = S.h_attn; d.meanA = S.mean_attn; d.rstdA = S.rstd_attn; d.qkv = S.qkv; d.xt_ln1 = (uint4*)S.xt_ln1; d.xt_o = (uint4*)S.xt_attn;
+        d.hM = S.h_mlp; d.meanM = S.mean_mlp; d.rstdM = S.rstd_mlp; d.pre = S.pre; d.xt_ln2 = (uint4*)S.xt_ln2; d.xt_a = (uint4*)S.xt_gelu;
+        stk::TrainGrad& o = a.grad[l];
+        o.dyt_fc2 = (__bf16*)G.dyt_fc2; o.dyt_fc1 = (__bf16*)G.dyt_fc1; o.dyt_proj = (__bf16*)G.dyt_proj; o.dyt_qkv = (__bf16*)G.dyt_qkv; o.part = G.part;
+    }
+    static OncePerDevice once;
+    if (once.first()) { allow_lds(stk::k_stack_train_bwd, stk::kTrainBwdLds); }
+    const int grid = lat::kGroups * 4 * ((f.n_seq + lat::kGroups - 1) / lat::kGroups);
+    hipLaunchKernelGGL(stk::k_stack_train_bwd, dim3(grid), dim3(kThreads), stk::kTrainBwdLds, (hipStream_t)stream, a);
+    return launched("k_stack_train_bwd launch");
+}
+
+// The weight gradients the backward chain left open: per block dW = dY^T . X for its four Linears - dY^T from syn_train_stack_bwd ([features][M] bf16),
+// X^T fragments from the forward - four GEMMs per launch; then the per-sequence partial sums of the bias / LayerNorm gradients added up.
+int syn_train_stack_wgrad(const syn_train_stack_grad* t, void* stream) {
+    if (!t || !t->fwd) return fail_msg("syn_train_stack_wgrad: null argument");
+    const syn_train_stack& f = *t->fwd;
+    const int M = 32 * f.n_seq;
+    if (f.n_seq < 1 || f.n_seq > 64 || M % 128) return fail_msg("syn_train_stack_wgrad: the row count must be a multiple of 128 (4 sequences)");
+    n128_setup();
+    hipStream_t s = (hipStream_t)stream;
+    stk::SmallOut so;
+    memset(&so, 0, sizeof(so));
+    if (t->first_block < t->last_block || t->last_block < 0 || t->first_block >= SYN_LAYERS) return fail_msg("syn_train_stack_wgrad: SYN_LAYERS > first_block >= last_block >= 0");
+    GQuadAll q;
+    memset(&q, 0, sizeof(q));
+    const int ns[4] = {512, 1024, 512, 1536}, ks[4] = {1024, 512, 512, 512};           // dW [n][k]: fc2, fc1, proj, qkv
+    int lds = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int mt = pick_mt128(ns[i], ks[i], M, 8);                // (64-row tiles for all four: 126 us for 8 launches against 182 with proj on 32-row tiles)
+        if (!mt) return fail_msg("syn_train_stack_wgrad: row count too large for the resident GEMM");
+        q.ns[i] = ns[i]; q.ks[i] = ks[i]; q.mt[i] = mt; q.gx[i] = (ns[i] + mt - 1) / mt;
+        q.cum[i + 1] = q.cum[i] + q.gx[i] * (ks[i] / 128);
+        lds = mt * M * 2 > lds ? mt * M * 2 : lds;
+    }
+    q.M = M; q.l0 = t->last_block;
+    for (int l = t->last_block; l <= t->first_block; ++l) {
+        const syn_train_block_save& S = f.save[l];
+        const syn_train_block_grad& G = t->grad[l];
+        if (!G.dw_fc2 || !G.dw_fc1 || !G.dw_proj || !G.dw_qkv || !G.d_ln2_g || !G.d_ln2_b || !G.d_fc2_b || !G.d_fc1_b || !G.d_ln1_g || !G.d_ln1_b || !G.d_proj_b) return fail_msg("syn_train_stack_wgrad: a block's gradient buffers are incomplete");
+        const void* xs[4] = {G.dyt_fc2, G.dyt_fc1, G.dyt_proj, G.dyt_qkv};
+        const void* ws[4] = {S.xt_gelu, S.xt_ln2, S.xt_attn, S.xt_ln1};
+        float* ys[4] = {G.dw_fc2, G.dw_fc1, G.dw_proj, G.dw_qkv};
+        for (int i = 0; i < 4; ++i) { q.X[l][i] = (const __bf16*)xs[i]; q.W[l][i] = (const uint4*)ws[i]; q.Y[l][i] = ys[i]; }
+        // bias / LayerNorm gradients: column sums over the sequences, in sequence order
+        float* const outs[7] = {G.d_ln2_g, G.d_ln2_b, G.d_fc2_b, G.d_fc1_b, G.d_ln1_g, G.d_ln1_b, G.d_proj_b};
+        so.part[l] = G.part;
+        for (int i = 0; i < 7; ++i) so.p[l][i] = outs[i];
+    }
+    // every block's four weight-gradient GEMMs in ONE launch (k_gemm_quad_all)
+    hipLaunchKernelGGL(k_gemm_quad_all, dim3(q.cum[4] * (t->first_block - t->last_block + 1)), dim3(kThreads), lds, s, q);
+    hipLaunchKernelGGL(stk::k_part_sums, dim3((stk::kPartCols + 255) / 256, t->first_block - t->last_block + 1), dim3(256), 0, s, f.n_seq, t->last_block, so);
+    return launched("syn_train_stack_wgrad");
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 //             packed copy every step.  Sequences are independent: no inter-workgroup traffic, two workgroup barriers per step.
 // Every output row is a k-ordered fma chain that does not depend on which rows share its tile: bitwise reproducible, and a sequence's
 // embedding does not depend on its batch.
+namespace {
 namespace t2m {
 
 constexpr int kBM = 64, kBN = 128, kKC = 64, kLdA = kKC + 4;       // row stride = 4 mod 64 words: the 16 x 4 float4 A reads spread over the banks
@@ -255,19 +256,6 @@ __global__ __launch_bounds__(256) void k_t2m_pack(const float* __restrict__ w, i
     reinterpret_cast<f32x4*>(out)[i] = v;
 }
 
-static int pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, int32_t layout, float* out, void* stream) {
-    if (!w || !out) return fail_msg("syn_t2m_pack_weight: null pointer");
-    if (n < 1 || k < 1 || n > (1 << 16) || k > (1 << 16) || conv_cin < 0 || (conv_cin > 0 && k != 4 * conv_cin))
-        return fail_msg("syn_t2m_pack_weight: n, k outside 1 .. 65536, or a convolution whose k is not 4 conv_cin");
-    if (layout != 0 && !((layout == SYN_T2M_TEXT_H || layout == SYN_T2M_MOTION_H) && n == 3 * layout && k == layout && conv_cin == 0))
-        return fail_msg("syn_t2m_pack_weight: layout is 0 (GEMM) or the GRU width H (512 / 1024) of a 3 H x H weight_hh");
-    const int kq = (int)(round_up(k, 16) / 16);
-    const long frags = layout == 0 ? round_up(n, kBN) / 16 * kq : (long)3 * layout / 16 * kq;
-    hipLaunchKernelGGL(k_t2m_pack, dim3((unsigned)((frags * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, (int)conv_cin,
-                       (int)layout, frags, kq, out);
-    return launched("k_t2m_pack launch");
-}
-
 static int gemm(hipStream_t st, int amode, GemmArgs g) {
     g.kq = (int)(round_up(g.k, 16) / 16);
     const dim3 grid((unsigned)((g.m + kBM - 1) / kBM), (unsigned)(round_up(g.n, kBN) / kBN));
@@ -292,23 +280,6 @@ struct Carve {
     float* take(long floats) { float* r = (float*)p; p += round_up(floats * 4, 256); return r; }
 };
 
-static long workspace_bytes(int32_t n_seq, int32_t max_len, int32_t kind) {
-    if (n_seq < 1 || n_seq > SYN_T2M_MAX_SEQ || (kind != SYN_T2M_MOTION && kind != SYN_T2M_TEXT)) return -1;
-    if (max_len < (kind == SYN_T2M_MOTION ? 4 : 1) || max_len > SYN_T2M_MAX_FRAMES) return -1;
-    Carve c = {nullptr};
-    const long n = n_seq;
-    if (kind == SYN_T2M_MOTION) {
-        const long t1 = conv_len(max_len), t2 = conv_len((int)t1);
-        c.take(n * t1 * SYN_T2M_MOVE); c.take(n * t2 * SYN_T2M_MOVE); c.take(n * t2 * SYN_T2M_MOVE);
-        c.take(n * t2 * SYN_T2M_MOTION_H); c.take(n * t2 * 6 * SYN_T2M_MOTION_H); c.take(n * 2 * SYN_T2M_MOTION_H); c.take(n * SYN_T2M_MOTION_H);
-    } else {
-        const long l = max_len;
-        c.take(n * l * SYN_T2M_WORD); c.take(n * l * SYN_T2M_TEXT_H); c.take(n * l * 6 * SYN_T2M_TEXT_H); c.take(n * 2 * SYN_T2M_TEXT_H);
-        c.take(n * SYN_T2M_TEXT_H);
-    }
-    return (long)(c.p - (char*)nullptr);
-}
-
 // gx -> final states -> Linear, LayerNorm + LeakyReLU (applied by the last GEMM's A load), Linear
 template <int H>
 static int recur_and_head(hipStream_t st, const syn_t2m_gru& r, const syn_t2m_head& hd, const float* gx, int n_seq, int max_len,
@@ -328,9 +299,45 @@ static int recur_and_head(hipStream_t st, const syn_t2m_gru& r, const syn_t2m_he
     return gemm(st, A_LN, g);
 }
 
-static int encode_motion(const syn_t2m_model* m, const float* motions, int32_t n_seq, int32_t n_frames, int32_t ld, const int32_t* lengths,
-                         const int32_t* order, void* workspace, float* out, void* stream) {
-    if (!m || !motions || !lengths || !order || !workspace || !out) return fail_msg("syn_t2m_encode_motion: null pointer");
+}  // namespace t2m
+}  // namespace
+
+extern "C" {
+
+int syn_t2m_pack_weight(const float* w, int32_t n, int32_t k, int32_t conv_cin, int32_t layout, float* out, void* stream) {
+    if (!w || !out) return fail_msg("syn_t2m_pack_weight: null pointer");
+    if (n < 1 || k < 1 || n > (1 << 16) || k > (1 << 16) || conv_cin < 0 || (conv_cin > 0 && k != 4 * conv_cin))
+        return fail_msg("syn_t2m_pack_weight: n, k outside 1 .. 65536, or a convolution whose k is not 4 conv_cin");
+    if (layout != 0 && !((layout == SYN_T2M_TEXT_H || layout == SYN_T2M_MOTION_H) && n == 3 * layout && k == layout && conv_cin == 0))
+        return fail_msg("syn_t2m_pack_weight: layout is 0 (GEMM) or the GRU width H (512 / 1024) of a 3 H x H weight_hh");
+    const int kq = (int)(t2m::round_up(k, 16) / 16);
+    const long frags = layout == 0 ? t2m::round_up(n, t2m::kBN) / 16 * kq : (long)3 * layout / 16 * kq;
+    hipLaunchKernelGGL(t2m::k_t2m_pack, dim3((unsigned)((frags * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, (int)conv_cin,
+                       (int)layout, frags, kq, out);
+    return launched("k_t2m_pack launch");
+}
+
+int64_t syn_t2m_workspace_bytes(int32_t n_seq, int32_t max_len, int32_t kind) {
+    if (n_seq < 1 || n_seq > SYN_T2M_MAX_SEQ || (kind != SYN_T2M_MOTION && kind != SYN_T2M_TEXT)) return -1;
+    if (max_len < (kind == SYN_T2M_MOTION ? 4 : 1) || max_len > SYN_T2M_MAX_FRAMES) return -1;
+    t2m::Carve c = {nullptr};
+    const long n = n_seq;
+    if (kind == SYN_T2M_MOTION) {
+        const long t1 = t2m::conv_len(max_len), t2 = t2m::conv_len((int)t1);
+        c.take(n * t1 * SYN_T2M_MOVE); c.take(n * t2 * SYN_T2M_MOVE); c.take(n * t2 * SYN_T2M_MOVE);
+        c.take(n * t2 * SYN_T2M_MOTION_H); c.take(n * t2 * 6 * SYN_T2M_MOTION_H); c.take(n * 2 * SYN_T2M_MOTION_H); c.take(n * SYN_T2M_MOTION_H);
+    } else {
+        const long l = max_len;
+        c.take(n * l * SYN_T2M_WORD); c.take(n * l * SYN_T2M_TEXT_H); c.take(n * l * 6 * SYN_T2M_TEXT_H); c.take(n * 2 * SYN_T2M_TEXT_H);
+        c.take(n * SYN_T2M_TEXT_H);
+    }
+    return (long)(c.p - (char*)nullptr);
+}
+
+int syn_t2m_encode_motion(const syn_t2m_model* m, const float* motions, int32_t n_seq, int32_t n_frames, int32_t ld, const int32_t* lengths_dev,
+                          const int32_t* order_dev, void* workspace, float* out, void* stream) {
+    using namespace t2m;
+    if (!m || !motions || !lengths_dev || !order_dev || !workspace || !out) return fail_msg("syn_t2m_encode_motion: null pointer");
     if (n_seq < 1 || n_seq > SYN_T2M_MAX_SEQ || n_frames < 4 || n_frames > SYN_T2M_MAX_FRAMES || ld < SYN_T2M_POSE)
         return fail_msg("syn_t2m_encode_motion: n_seq outside 1 .. SYN_T2M_MAX_SEQ, n_frames outside 4 .. SYN_T2M_MAX_FRAMES, or ld < 619");
     if (!m->conv1_w || !m->conv1_b || !m->conv2_w || !m->conv2_b || !m->out_w || !m->out_b || !m->motion_in_w || !m->motion_in_b ||
@@ -340,7 +347,7 @@ static int encode_motion(const syn_t2m_model* m, const float* motions, int32_t n
     const int t1 = conv_len(n_frames), t2 = conv_len(t1);
     const long n = n_seq;
     constexpr int H = SYN_T2M_MOTION_H, C = SYN_T2M_MOVE;
-    Carve ws = {(char*)workspace};                              // the order of workspace_bytes
+    Carve ws = {(char*)workspace};                              // the order of syn_t2m_workspace_bytes
     float* c1 = ws.take(n * t1 * C); float* c2 = ws.take(n * t2 * C); float* mv = ws.take(n * t2 * C);
     float* emb = ws.take(n * t2 * H); float* gx = ws.take(n * t2 * 6 * H); float* hcat = ws.take(n * 2 * H); float* y1 = ws.take(n * H);
     GemmArgs g = {};
@@ -352,12 +359,13 @@ static int encode_motion(const syn_t2m_model* m, const float* motions, int32_t n
     if (int rc = linear(st, c2, C, n * t2, C, C, m->out_w, m->out_b, E_BIAS, mv, C)) return rc;
     if (int rc = linear(st, mv, C, n * t2, C, H, m->motion_in_w, m->motion_in_b, E_BIAS, emb, H)) return rc;
     if (int rc = linear(st, emb, H, n * t2, H, 6 * H, m->motion_gru.w_ih, m->motion_gru.b_ih, E_BIAS, gx, 6 * H)) return rc;
-    return recur_and_head<H>(st, m->motion_gru, m->motion_head, gx, n_seq, t2, lengths, order, hcat, y1, out);
+    return recur_and_head<H>(st, m->motion_gru, m->motion_head, gx, n_seq, t2, lengths_dev, order_dev, hcat, y1, out);
 }
 
-static int encode_text(const syn_t2m_model* m, const float* word_embs, const float* pos_onehot, int32_t n_seq, int32_t max_len,
-                       const int32_t* lengths, const int32_t* order, void* workspace, float* out, void* stream) {
-    if (!m || !word_embs || !pos_onehot || !lengths || !order || !workspace || !out) return fail_msg("syn_t2m_encode_text: null pointer");
+int syn_t2m_encode_text(const syn_t2m_model* m, const float* word_embs, const float* pos_onehot, int32_t n_seq, int32_t max_len,
+                        const int32_t* lengths_dev, const int32_t* order_dev, void* workspace, float* out, void* stream) {
+    using namespace t2m;
+    if (!m || !word_embs || !pos_onehot || !lengths_dev || !order_dev || !workspace || !out) return fail_msg("syn_t2m_encode_text: null pointer");
     if (n_seq < 1 || n_seq > SYN_T2M_MAX_SEQ || max_len < 1 || max_len > SYN_T2M_MAX_FRAMES)
         return fail_msg("syn_t2m_encode_text: n_seq outside 1 .. SYN_T2M_MAX_SEQ or max_len outside 1 .. SYN_T2M_MAX_FRAMES");
     if (!m->pos_w || !m->pos_b || !m->text_in_w || !m->text_in_b || !gru_ok(m->text_gru) || !head_ok(m->text_head))
@@ -371,6 +379,7 @@ static int encode_text(const syn_t2m_model* m, const float* word_embs, const flo
     if (int rc = linear(st, pos_onehot, SYN_T2M_POS, rows, SYN_T2M_POS, W, m->pos_w, m->pos_b, E_ADD, x0, W, word_embs, W)) return rc;
     if (int rc = linear(st, x0, W, rows, W, H, m->text_in_w, m->text_in_b, E_BIAS, emb, H)) return rc;
     if (int rc = linear(st, emb, H, rows, H, 6 * H, m->text_gru.w_ih, m->text_gru.b_ih, E_BIAS, gx, 6 * H)) return rc;
-    return recur_and_head<H>(st, m->text_gru, m->text_head, gx, n_seq, max_len, lengths, order, hcat, y1, out);
+    return recur_and_head<H>(st, m->text_gru, m->text_head, gx, n_seq, max_len, lengths_dev, order_dev, hcat, y1, out);
 }
-}  // namespace t2m
+
+}  // extern "C"

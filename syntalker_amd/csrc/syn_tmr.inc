@@ -5,6 +5,7 @@
 // (embedding + pe + tokens, bias, GELU, or bias + residual + LayerNorm); attention is k_tmr_attn (a workgroup per sequence, head and 64 queries).
 // The last layer runs its queries, out_proj, FFN and both LayerNorms on rows 0-1 of each sequence only ("head rows").
 // syn_bert.inc uses this file's tile constants, split8 / load8, the packed-weight layout (k_tmr_pack) and `launched`.
+namespace {
 namespace tmr {
 
 constexpr int kD = 256, kQKV = 768, kFF = 1024, kHeads = 4, kHd = 64, kMaxS = 256;
@@ -334,17 +335,23 @@ int gemm(const GemmArgs& a, int n_cols, hipStream_t st) {
     return launched("k_tmr_gemm launch");
 }
 
-static int pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream) {
+}  // namespace tmr
+}  // namespace
+
+extern "C" {
+
+int syn_tmr_pack_weight(const float* w, int32_t n, int32_t k, void* out, void* stream) {
     if (!w || !out || n < 16 || n % 16 || k < 1 || k > SYN_TMR_MAX_FEATS)
         return fail_msg("syn_tmr_pack_weight: null pointer, rows not a positive multiple of 16, or columns outside 1 .. SYN_TMR_MAX_FEATS");
     const int ks = (k + 31) / 32;
     const long total = (long)n / 16 * ks * 64;
-    hipLaunchKernelGGL(k_tmr_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, ks, (bf16x8*)out);
+    hipLaunchKernelGGL(tmr::k_tmr_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)n, (int)k, ks, (bf16x8*)out);
     return launched("k_tmr_pack launch");
 }
 
-static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
-                  float* mu, float* logvar, void* stream) {
+int syn_tmr_encode(const syn_tmr_model* m, const float* features, int32_t n_seq, int32_t max_len, const int32_t* lengths, void* workspace,
+                   float* mu, float* logvar, void* stream) {
+    using namespace tmr;
     if (!m || !features || !workspace || !mu || !logvar) return fail_msg("syn_tmr_encode: null pointer");
     if (n_seq < 1 || n_seq > SYN_TMR_MAX_SEQ || max_len < 1 || max_len > SYN_TMR_MAX_LEN)
         return fail_msg("syn_tmr_encode: n_seq outside 1 .. SYN_TMR_MAX_SEQ or max_len outside 1 .. SYN_TMR_MAX_LEN");
@@ -394,7 +401,7 @@ static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, 
         if ((rc = gemm<EPI_LN>(p, kD, st))) return rc;
         GemmArgs f = t;                                        // linear1 + GELU
         f.a = x; f.w = (const bf16x8*)y.w_fc1; f.n_frag_cols = kFF / 16; f.bias = y.b_fc1; f.out_f = hid; f.ld_out = kFF;
-        if ((rc = gemm<EPI_GELU>(f, kFF, st))) return rc;
+        if ((rc = gemm<tmr::EPI_GELU>(f, kFF, st))) return rc;
         GemmArgs s = t;                                        // linear2 + residual + norm2 (the last layer's rows 0 / 1 are mu / logvar)
         s.a = hid; s.lda = kFF; s.K = kFF; s.KS = kFF / 32; s.a_mapped = 0; s.w = (const bf16x8*)y.w_fc2; s.bias = y.b_fc2;
         s.res = x; s.out_f = x; s.ln_g = y.ln2_g; s.ln_b = y.ln2_b;
@@ -403,4 +410,5 @@ static int encode(const syn_tmr_model* m, const float* features, int32_t n_seq, 
     }
     return rc;
 }
-}  // namespace tmr
+
+}  // extern "C"

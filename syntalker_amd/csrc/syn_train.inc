@@ -1,9 +1,11 @@
 // syn_train.inc — fp32 forward / backward kernels of the non-GEMM pieces of a transformer block, for the
 // training path (SURVEY.md §8 a10; reference models/timm_transformer/transformer.py:56-104 Attention,
-// :117-151 Mlp, :154-198 Block).  Included by syn_kernels.hip.  The Linear layers (forward, dgrad, wgrad) already
+// :117-151 Mlp, :154-198 Block).  Included by syn_kernels.hip; entry points (syn_ln_*, syn_gelu_*, syn_attn_*,
+// syn_bn_*, syn_opt_*, syn_linear_bwd_prep / _wgrad_rows) at the end.  The Linear layers (forward, dgrad, wgrad) already
 // run on the MFMA GEMM (syn_linear); these kernels replace the ~40 elementwise / reduction launches per block
 // that the PyTorch-ROCm ops cost.  fp32 everywhere: they sit between bf16-operand GEMMs and must not add error.
 
+namespace {
 namespace trn {
 
 __device__ __forceinline__ float warp_sum(float v) {
@@ -842,3 +844,265 @@ __global__ __launch_bounds__(256) void k_opt_adam(const OptList L, const float* 
 }
 
 }  // namespace trn
+}  // namespace
+
+// ---- entry points (include/syn_hip.h) ----------------------------------------------------------------------------------------------------
+extern "C" {
+
+// ---- training path: fp32 forward / backward of LayerNorm(512), GELU and the 32-token attention ---------------
+int syn_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* mean, float* rstd, int32_t rows, void* stream) {
+    if (!x || !gamma || !beta || (!y && !y_bf16) || !mean || !rstd || rows <= 0) return fail_msg("syn_ln_fwd: bad arguments");
+    hipLaunchKernelGGL(trn::k_ln_fwd, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, (__bf16*)y_bf16, mean, rstd, rows);
+    return launched("k_ln_fwd launch");
+}
+
+int syn_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
+               float* dgamma, float* dbeta, float* scratch, int32_t rows, void* stream) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !scratch || rows <= 0) return fail_msg("syn_ln_bwd: bad arguments");
+    const int per = 16, nwg = (rows + per - 1) / per;             // scratch: [nwg][2][512] floats (16 rows per workgroup: 1024 rows = 64 workgroups;
+                                                                  // with 64 rows the 16 workgroups walked their rows one dependent load after the other, 14 us)
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(trn::k_ln_bwd, dim3(nwg), dim3(256), 0, s, dy, x, gamma, mean, rstd, add, dx, scratch, rows, per);
+    hipLaunchKernelGGL(trn::k_colsum, dim3(4), dim3(256), 0, s, scratch, nwg, 2 * SYN_D, SYN_D, dgamma, dbeta);   // partials [p][dgamma | dbeta]
+    return launched("k_ln_bwd launch");
+}
+
+int syn_gelu_fwd(const float* x, float* y, void* y_bf16, int64_t n, void* stream) {
+    if (!x || (!y && !y_bf16) || n <= 0 || n % 4) return fail_msg("syn_gelu_fwd: n must be a positive multiple of 4");
+    hipLaunchKernelGGL(trn::k_gelu_fwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, (__bf16*)y_bf16, (size_t)(n / 4));
+    return launched("k_gelu_fwd launch");
+}
+
+int syn_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
+    if (!x || !dy || !dx || n <= 0 || n % 4) return fail_msg("syn_gelu_bwd: n must be a positive multiple of 4");
+    hipLaunchKernelGGL(trn::k_gelu_bwd, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, (size_t)(n / 4));
+    return launched("k_gelu_bwd launch");
+}
+
+int syn_linear_wgrad_rows(const float* dy, const void* x_bf16, int32_t m_rows, int32_t n, int32_t k, float* dw, float* db, void* stream) {
+    if (!dy || !x_bf16 || !dw || m_rows <= 0 || m_rows > 64 || n <= 0 || n % 16 || k <= 0)
+        return fail_msg("syn_linear_wgrad_rows: 1 .. 64 rows, n a multiple of 16");
+    hipLaunchKernelGGL(trn::k_linear_wgrad_rows, dim3((k + 255) / 256, n / 16), dim3(256), 0, (hipStream_t)stream, dy, (const __bf16*)x_bf16, m_rows, n, k, dw, db);
+    return launched("k_linear_wgrad_rows launch");
+}
+
+int32_t syn_bn_chunks(int64_t rows) { const int cr = trn::bn_chunk_rows((long)rows); return (int32_t)((rows + cr - 1) / cr); }
+
+int syn_bn_act_fwd(const float* y, const float* shortcut, int64_t rows, int32_t channels, const float* gamma, const float* beta, float eps,
+                   float momentum, float* run_mean, float* run_var, const float* conv_bias, int32_t act, float* ws, int32_t ws_chunks, float* stats,
+                   float* z, void* stream) {
+    if (!y || !gamma || !beta || !ws || !stats || !z || rows <= 0 || channels <= 0 || channels % 4 || 256 % (channels / 4) || channels > 1024)
+        return fail_msg("syn_bn_act_fwd: need channels in {4 .. 1024} with channels / 4 dividing 256, rows > 0, non-null pointers");
+    hipStream_t s = (hipStream_t)stream;
+    // ws_chunks > 0: ws already holds that many [2][channels] partial sums (written by the convolution's epilogue, syn_conv1d_train_fwd)
+    const int chunks = ws_chunks > 0 ? ws_chunks : syn_bn_chunks(rows);
+    if (ws_chunks <= 0) hipLaunchKernelGGL(trn::k_bn_stats, dim3(chunks), dim3(256), 0, s, y, (long)rows, channels, ws);
+    hipLaunchKernelGGL(trn::k_bn_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, (long)rows, eps, momentum,
+                       stats, run_mean, run_var, conv_bias);
+    const long n4 = rows * channels / 4;
+    hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
+                       act, z);
+    return launched("syn_bn_act_fwd");
+}
+
+int syn_bn_act_bwd(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
+                   int32_t channels, int32_t act, float* ws, float* dgamma_dbeta, float* dy, float* dshortcut, void* stream) {
+    if (!dz || !y || !stats || !gamma || !ws || !dgamma_dbeta || !dy || rows <= 0 || channels % 4 || 256 % (channels / 4))
+        return fail_msg("syn_bn_act_bwd: bad arguments");
+    if (act && !z && (dshortcut || !beta)) return fail_msg("syn_bn_act_bwd: z may only be omitted (with beta given) when no shortcut entered the activation");
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = syn_bn_chunks(rows);
+    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
+    hipLaunchKernelGGL(trn::k_bn_bwd_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgamma_dbeta);
+    const long n4 = rows * channels / 4;
+    hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)dgamma_dbeta,
+                       channels, n4, (long)rows, act, dy, dshortcut);
+    return launched("syn_bn_act_bwd");
+}
+
+/* ---- the fused tail of a BasicBlock: statistics -> per-channel affine; one elementwise pass per block and direction ---- */
+static bool bn_shape_ok(int64_t rows, int32_t channels) { return rows > 0 && channels > 0 && channels % 4 == 0 && 256 % (channels / 4) == 0 && channels <= 1024; }
+
+int syn_bn_finalize(const float* part, int32_t chunks, int64_t rows, int32_t channels, const float* gamma, const float* beta, float eps, float momentum,
+                    float* run_mean, float* run_var, const float* conv_bias, float* stats, float* affine, void* stream) {
+    if (!part || chunks <= 0 || !gamma || !beta || !stats || !affine || !bn_shape_ok(rows, channels)) return fail_msg("syn_bn_finalize: bad arguments");
+    hipLaunchKernelGGL(trn::k_bn_finalize_aff, dim3(channels), dim3(256), 0, (hipStream_t)stream, part, chunks, channels, (long)rows, eps, momentum, gamma, beta,
+                       stats, affine, run_mean, run_var, conv_bias);
+    return launched("syn_bn_finalize");
+}
+
+int syn_bn_finalize_pair(const syn_bn_finalize_job* a, const syn_bn_finalize_job* b, void* stream) {
+    if (!a || !b) return fail_msg("syn_bn_finalize_pair: two jobs");
+    trn::FinJob j[2];
+    const syn_bn_finalize_job* q[2] = {a, b};
+    for (int i = 0; i < 2; ++i) {
+        if (!q[i]->part || q[i]->chunks <= 0 || !q[i]->gamma || !q[i]->beta || !q[i]->stats || !q[i]->affine || !bn_shape_ok(q[i]->rows, q[i]->channels))
+            return fail_msg("syn_bn_finalize_pair: bad arguments");
+        j[i].part = q[i]->part; j[i].chunks = q[i]->chunks; j[i].C = q[i]->channels; j[i].rows = (long)q[i]->rows; j[i].eps = q[i]->eps; j[i].momentum = q[i]->momentum;
+        j[i].gamma = q[i]->gamma; j[i].beta = q[i]->beta; j[i].stats = q[i]->stats; j[i].aff = q[i]->affine;
+        j[i].run_mean = q[i]->run_mean; j[i].run_var = q[i]->run_var; j[i].conv_bias = q[i]->conv_bias;
+    }
+    hipLaunchKernelGGL(trn::k_bn_finalize_aff2, dim3(j[0].C + j[1].C), dim3(256), 0, (hipStream_t)stream, j[0], j[1]);
+    return launched("syn_bn_finalize_pair");
+}
+
+int syn_bn_apply2(const float* y, const float* affine, const float* shortcut, const float* short_affine, int64_t rows, int32_t channels, int32_t act,
+                  float* z, void* stream) {
+    if (!y || !affine || !z || !bn_shape_ok(rows, channels) || (short_affine && !shortcut)) return fail_msg("syn_bn_apply2: bad arguments");
+    const long n4 = rows * channels / 4;
+    hipLaunchKernelGGL(trn::k_bn_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, affine, shortcut, short_affine, channels, n4, act, z);
+    return launched("syn_bn_apply2");
+}
+
+int syn_bn_block_bwd(const float* dz, const float* y, const float* shortcut, const float* stats, const float* affine, const float* short_stats,
+                     const float* short_affine, int64_t rows, int32_t channels, int32_t act, float* ws, float* dgb, float* short_dgb, float* dy,
+                     float* dshortcut, void* stream) {
+    if (!dz || !y || !stats || !affine || !ws || !dgb || !bn_shape_ok(rows, channels)) return fail_msg("syn_bn_block_bwd: bad arguments");
+    if (!dy && dshortcut) return fail_msg("syn_bn_block_bwd: dy NULL (statistics and dgamma / dbeta only) takes no dshortcut either");
+    if ((short_affine != nullptr) != (short_stats != nullptr) || (short_affine && (!shortcut || !short_dgb || (dy && !dshortcut))))
+        return fail_msg("syn_bn_block_bwd: a normalised shortcut needs its tensor, statistics, affine, gradient buffer and dshortcut");
+    if (dshortcut && !shortcut) return fail_msg("syn_bn_block_bwd: dshortcut without a shortcut");
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = syn_bn_chunks(rows);
+    hipLaunchKernelGGL(trn::k_bn_bwd_stats2, dim3(chunks), dim3(256), 0, s, dz, y, shortcut, stats, affine, short_stats, short_affine, (long)rows, channels, act, ws);
+    hipLaunchKernelGGL(trn::k_bn_bwd_finalize2, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgb, short_affine ? short_dgb : nullptr);
+    const long n4 = rows * channels / 4;
+    if (dy)                                                   // (dy NULL: the caller's next kernel forms dy / dshortcut itself - syn_conv1d_first_wgrad_tail)
+        hipLaunchKernelGGL(trn::k_bn_bwd_apply2, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, y, shortcut, stats, affine, short_stats, short_affine,
+                           (const float*)dgb, (const float*)short_dgb, channels, n4, (long)rows, act, dy, dshortcut);
+    return launched("syn_bn_block_bwd");
+}
+
+/* ---- nn.SyncBatchNorm on the same kernels: sums -> (the caller's all-reduce) -> apply ---- */
+int syn_bn_sums(const float* y, int64_t rows, int32_t channels, float* ws, int32_t ws_chunks, double* sums, void* stream) {
+    if (!ws || !sums || rows <= 0 || channels <= 0 || channels % 4 || 256 % (channels / 4) || channels > 1024 || (ws_chunks <= 0 && !y))
+        return fail_msg("syn_bn_sums: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = ws_chunks > 0 ? ws_chunks : syn_bn_chunks(rows);
+    if (ws_chunks <= 0) hipLaunchKernelGGL(trn::k_bn_stats, dim3(chunks), dim3(256), 0, s, y, (long)rows, channels, ws);
+    hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
+    return launched("syn_bn_sums");
+}
+
+int syn_bn_act_apply(const float* y, const float* shortcut, int64_t rows, int64_t rows_total, int32_t channels, const float* gamma, const float* beta,
+                     float eps, float momentum, float* run_mean, float* run_var, const float* conv_bias, int32_t act, const double* sums_total,
+                     float* stats, float* z, void* stream) {
+    if (!y || !gamma || !beta || !sums_total || !stats || !z || rows <= 0 || rows_total < rows || channels <= 0 || channels % 4)
+        return fail_msg("syn_bn_act_apply: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(trn::k_bn_finalize64, dim3((channels + 255) / 256), dim3(256), 0, s, sums_total, channels, (long)rows_total, eps, momentum, stats,
+                       run_mean, run_var, conv_bias);
+    const long n4 = rows * channels / 4;
+    hipLaunchKernelGGL(trn::k_bn_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, y, shortcut, (const float*)stats, gamma, beta, channels, n4,
+                       act, z);
+    return launched("syn_bn_act_apply");
+}
+
+int syn_bn_bwd_sums(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
+                    int32_t channels, int32_t act, float* ws, double* sums, void* stream) {
+    if (!dz || !y || !stats || !gamma || !ws || !sums || rows <= 0 || channels % 4 || 256 % (channels / 4))
+        return fail_msg("syn_bn_bwd_sums: bad arguments");
+    if (act && !z && !beta) return fail_msg("syn_bn_bwd_sums: z may only be omitted with beta given");
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = syn_bn_chunks(rows);
+    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
+    hipLaunchKernelGGL(trn::k_bn_sums64, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, sums);
+    return launched("syn_bn_bwd_sums");
+}
+
+int syn_bn_act_bwd_apply(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta,
+                         const double* sums_local, const double* sums_total, int64_t rows, int64_t rows_total, int32_t channels, int32_t act,
+                         float* dgamma_dbeta, float* scratch, float* dy, float* dshortcut, void* stream) {
+    if (!dz || !y || !stats || !gamma || !sums_local || !sums_total || !dgamma_dbeta || !scratch || !dy || rows <= 0 || rows_total < rows || channels % 4)
+        return fail_msg("syn_bn_act_bwd_apply: bad arguments");
+    if (act && !z && (dshortcut || !beta)) return fail_msg("syn_bn_act_bwd_apply: z may only be omitted (with beta given) when no shortcut entered the activation");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(trn::k_bn_bwd_unpack64, dim3((channels + 255) / 256), dim3(256), 0, s, sums_local, sums_total, channels, dgamma_dbeta, scratch);
+    const long n4 = rows * channels / 4;
+    hipLaunchKernelGGL(trn::k_bn_bwd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (const float*)scratch,
+                       channels, n4, (long)rows_total, act, dy, dshortcut);
+    return launched("syn_bn_act_bwd_apply");
+}
+
+int syn_linear_bwd_prep(const float* dy, int32_t ld, int32_t row_div, float const_scale, int32_t m_rows, int32_t n, const float* row_scale,
+                        int32_t rows_per_scale, void* dy_bf16, void* dy_bf16_t, float* colsum_part, void* stream) {
+    if (!dy || !dy_bf16 || !dy_bf16_t || m_rows <= 0 || n <= 0 || m_rows % 64 || n % 64 || (row_scale && rows_per_scale <= 0) || ld < n || ld % 4 || row_div < 1)
+        return fail_msg("syn_linear_bwd_prep: need m_rows % 64 == 0, n % 64 == 0, ld >= n, ld % 4 == 0, row_div >= 1 and non-null pointers");
+    hipLaunchKernelGGL(trn::k_linear_bwd_prep, dim3(n / 64, m_rows / 64), dim3(256), 0, (hipStream_t)stream, dy, ld, row_div, const_scale, m_rows, n, row_scale,
+                       rows_per_scale, (__bf16*)dy_bf16, (__bf16*)dy_bf16_t, colsum_part);
+    return launched("k_linear_bwd_prep launch");
+}
+
+// ---- optimizer step (clip + Adam) over lists of <= 64 tensors ------------------------------------------------------------------------------------
+static int opt_fill(trn::OptList& L, const syn_opt_list* l, const char* who) {
+    static_assert(SYN_OPT_MAX == trn::kOptMax, "include/syn_hip.h: tensors per optimizer list");
+    if (!l || l->n <= 0 || l->n > SYN_OPT_MAX) return fail_msg(who);
+    int blocks = 0;
+    for (int i = 0; i < l->n; ++i) {
+        if (!l->g[i] || l->numel[i] <= 0) return fail_msg(who);
+        L.p[i] = l->p[i]; L.g[i] = l->g[i]; L.m[i] = l->m[i]; L.v[i] = l->v[i]; L.numel[i] = l->numel[i];
+        L.first[i] = blocks;
+        blocks += (l->numel[i] + trn::kOptChunk - 1) / trn::kOptChunk;
+    }
+    L.first[l->n] = blocks; L.n = l->n;
+    return 0;
+}
+
+int32_t syn_opt_blocks(const syn_opt_list* l) {
+    if (!l || l->n <= 0 || l->n > SYN_OPT_MAX) return -1;
+    int blocks = 0;
+    for (int i = 0; i < l->n; ++i) blocks += (l->numel[i] + trn::kOptChunk - 1) / trn::kOptChunk;
+    return blocks;
+}
+
+int syn_opt_sqnorm(const syn_opt_list* l, float* partials, void* stream) {
+    trn::OptList L;
+    if (!partials) return fail_msg("syn_opt_sqnorm: partials is NULL");
+    if (int rc = opt_fill(L, l, "syn_opt_sqnorm: need 1 .. 64 tensors with gradients")) return rc;
+    hipLaunchKernelGGL(trn::k_opt_sqnorm, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, partials);
+    return launched("k_opt_sqnorm launch");
+}
+
+int syn_opt_scalars(const float* partials, int32_t n_partials, float max_norm, const float* lr_dev, float lr, float beta1, float beta2, float* step_dev,
+                    float* scal4, void* stream) {
+    if ((n_partials > 0 && !partials) || n_partials < 0 || !step_dev || !scal4) return fail_msg("syn_opt_scalars: bad arguments");
+    hipLaunchKernelGGL(trn::k_opt_scalars, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, max_norm, lr_dev, lr, beta1, beta2, step_dev, scal4);
+    return launched("k_opt_scalars launch");
+}
+
+int syn_opt_adam(const syn_opt_list* l, const float* scal4, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+    trn::OptList L;
+    if (!scal4) return fail_msg("syn_opt_adam: scal4 is NULL");
+    if (int rc = opt_fill(L, l, "syn_opt_adam: need 1 .. 64 tensors")) return rc;
+    for (int i = 0; i < L.n; ++i) if (!L.p[i] || !L.m[i] || !L.v[i]) return fail_msg("syn_opt_adam: null parameter / moment pointer");
+    hipLaunchKernelGGL(trn::k_opt_adam, dim3(L.first[L.n]), dim3(256), 0, (hipStream_t)stream, L, scal4, beta1, beta2, eps, weight_decay);
+    return launched("k_opt_adam launch");
+}
+
+int syn_attn_fwd(const float* qkv, float* o, void* o_bf16, int32_t n_seq, void* stream) {
+    if (!qkv || (!o && !o_bf16) || n_seq <= 0) return fail_msg("syn_attn_fwd: bad arguments");
+    hipLaunchKernelGGL(trn::k_attn_fwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnFwd2Lds, (hipStream_t)stream, qkv, o, (__bf16*)o_bf16);
+    return launched("k_attn_fwd launch");
+}
+
+int syn_attn_bwd(const float* qkv, const float* d_o, float* dqkv, int32_t n_seq, void* stream) {
+    if (!qkv || !d_o || !dqkv || n_seq <= 0) return fail_msg("syn_attn_bwd: bad arguments");
+    static OncePerDevice once;
+    if (once.first()) allow_lds(trn::k_attn_bwd2, trn::kAttnBwd2Lds);
+    hipLaunchKernelGGL(trn::k_attn_bwd2, dim3(n_seq * SYN_HEADS), dim3(256), trn::kAttnBwd2Lds, (hipStream_t)stream, qkv, d_o, dqkv);
+    return launched("k_attn_bwd launch");
+}
+
+// backward statistics of a BatchNorm (+ activation) alone - dgamma_dbeta [3][channels] - for a consumer that forms dy itself (syn_conv1d_first_wgrad_bn)
+int syn_bn_bwd_stats(const float* dz, const float* z, const float* y, const float* stats, const float* gamma, const float* beta, int64_t rows,
+                     int32_t channels, int32_t act, float* ws, float* dgamma_dbeta, void* stream) {
+    if (!dz || !y || !stats || !gamma || !ws || !dgamma_dbeta || rows <= 0 || channels % 4 || 256 % (channels / 4)) return fail_msg("syn_bn_bwd_stats: bad arguments");
+    if (act && !z && !beta) return fail_msg("syn_bn_bwd_stats: without z the activation's sign is recomputed and needs beta");
+    hipStream_t s = (hipStream_t)stream;
+    const int chunks = syn_bn_chunks(rows);
+    hipLaunchKernelGGL(trn::k_bn_bwd_stats, dim3(chunks), dim3(256), 0, s, dz, z, y, stats, gamma, beta, (long)rows, channels, act, ws);
+    hipLaunchKernelGGL(trn::k_bn_bwd_finalize, dim3(channels), dim3(256), 0, s, (const float*)ws, chunks, channels, dgamma_dbeta);
+    return launched("syn_bn_bwd_stats");
+}
+
+}  // extern "C"

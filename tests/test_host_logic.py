@@ -240,21 +240,52 @@ def test_c_abi_library_exports_every_declared_symbol():
     missing = [n for n in _lib.EXPORTS if n not in no_args and getattr(loaded, n).argtypes is None]
     assert not missing, missing
     # struct sizes exactly as the C compiler lays out include/syn_hip.h (gcc, same ABI as hipcc's host side)
+    # every struct the header declares and the ctypes bindings mirror (r6: syn_wgrad_sum_job grew a field); syn_pack_job alone has no mirror
+    # (callers fill a device array of them from a tensor)
     import subprocess, tempfile
+    mirrors = {"syn_step": _lib.SynStep, "syn_layer": _lib.SynLayer, "syn_model": _lib.SynModel, "syn_wavenc": _lib.SynWavEnc, "syn_vq_model": _lib.SynVqModel,
+               "syn_train_block_save": _lib.SynTrainBlockSave, "syn_train_stack": _lib.SynTrainStack, "syn_train_block_grad": _lib.SynTrainBlockGrad,
+               "syn_train_stack_grad": _lib.SynTrainStackGrad, "syn_opt_list": _lib.SynOptList, "syn_concat_src": _lib.SynConcatSrc,
+               "syn_wgrad_sum_job": _lib.SynWgradSumJob, "syn_bn_finalize_job": _lib.SynBnFinalizeJob, "syn_conv_pack_req": _lib.SynConvPackReq,
+               "syn_wav_conv": _lib.SynWavConv, "syn_cond_weights": _lib.SynCondWeights, "syn_vq_conv": _lib.SynVqConv,
+               "syn_edit": _lib.SynEdit, "syn_plms_row": _lib.SynPlmsRow, "syn_bpd_row": _lib.SynBpdRow,
+               "syn_tmr_layer": _lib.SynTmrLayer, "syn_tmr_model": _lib.SynTmrModel, "syn_bert_layer": _lib.SynBertLayer, "syn_bert_model": _lib.SynBertModel,
+               "syn_skel_layer": _lib.SynSkelLayer, "syn_skel_model": _lib.SynSkelModel,
+               "syn_t2m_gru": _lib.SynT2mGru, "syn_t2m_head": _lib.SynT2mHead, "syn_t2m_model": _lib.SynT2mModel}
+    assert set(re.findall(r"typedef struct (syn_\w+)", header)) == set(mirrors) | {"syn_pack_job"}
     with tempfile.TemporaryDirectory() as td:
         src = os.path.join(td, "sz.c")
-        open(src, "w").write('#include <stdio.h>\n#include "syn_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu", sizeof(syn_step), '
-                             'sizeof(syn_layer), sizeof(syn_model), sizeof(syn_wavenc), sizeof(syn_vq_model));'
-                             'printf(" %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(syn_train_block_save), sizeof(syn_train_stack), sizeof(syn_train_block_grad), '
-                             'sizeof(syn_train_stack_grad), sizeof(syn_opt_list), sizeof(syn_concat_src), sizeof(syn_wgrad_sum_job), sizeof(syn_bn_finalize_job), '
-                             'sizeof(syn_conv_pack_req), sizeof(syn_wav_conv), sizeof(syn_cond_weights), sizeof(syn_vq_conv));return 0;}\n')
+        open(src, "w").write('#include <stdio.h>\n#include "syn_hip.h"\nint main(void){'
+                             + "".join(f'printf("%zu ", sizeof({name}));' for name in mirrors) + "return 0;}\n")
         subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), src, "-o", os.path.join(td, "sz")], check=True)
         sizes = [int(v) for v in subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout.split()]
-    mirrors = (_lib.SynStep, _lib.SynLayer, _lib.SynModel, _lib.SynWavEnc, _lib.SynVqModel, _lib.SynTrainBlockSave, _lib.SynTrainStack, _lib.SynTrainBlockGrad,
-               _lib.SynTrainStackGrad, _lib.SynOptList, _lib.SynConcatSrc, _lib.SynWgradSumJob, _lib.SynBnFinalizeJob, _lib.SynConvPackReq, _lib.SynWavConv,
-               _lib.SynCondWeights, _lib.SynVqConv)                    # every struct the ctypes bindings mirror (r6: syn_wgrad_sum_job grew a field)
-    assert sizes == [ctypes.sizeof(c) for c in mirrors], (sizes, [ctypes.sizeof(c) for c in mirrors])
+    assert sizes == [ctypes.sizeof(c) for c in mirrors.values()], (sizes, [ctypes.sizeof(c) for c in mirrors.values()])
     assert sizes[0] == 16 + 8 * 23 + 8 and sizes[2] == 8 * 5 + 88 * 8 + 16 + 24
+
+
+def test_ctypes_signatures_are_read_from_the_header():
+    """The binding is derived from include/syn_hip.h's prototypes: the exact argtypes / restype of entry points that between them use every mapped type
+    and both pointer rules, and a prototype of an unmapped type is refused by name instead of being bound with ctypes' default.  No library needed."""
+    from syntalker_amd import _lib
+    vp, i32, i64, u64, f32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
+    protos = _lib.prototypes(open(os.path.join(REPO, "include", "syn_hip.h")).read())
+    assert protos == _lib.PROTOTYPES and len(protos) == len(_lib.EXPORTS) + len(_lib.DIAGNOSTICS) and not set(_lib.EXPORTS) & set(_lib.DIAGNOSTICS)
+    want = {
+        "syn_denoise_steps": (ctypes.c_int, [ctypes.POINTER(_lib.SynModel), ctypes.POINTER(_lib.SynStep), i32, i32, i32, vp]),    # struct pointers, int32_t
+        "syn_randn": (ctypes.c_int, [vp, i64, u64, u64, i64, vp]),                                                                # int64_t, uint64_t
+        "syn_beat_align": (ctypes.c_int, [vp, i32, i32, i32, vp, i32, vp, vp, f64, f32, vp, vp, vp]),                             # double, float, uint8_t*, double*
+        "syn_plms_update": (ctypes.c_int, [vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]),                                           # a device table stays c_void_p
+        "syn_l1div_workspace_bytes": (i64, [i32, i64, i32]),
+        "syn_vq_train_loss_parts": (i32, [i64, i32]),
+        "syn_last_error": (ctypes.c_char_p, []),
+        "syn_debug_timing": (None, [vp, vp]),
+    }
+    for name, sig in want.items():
+        assert protos[name] == sig, (name, protos[name])
+    for bad in ("int syn_bad_arg(const float* x, long double scale, void* stream);", "long double syn_bad_ret(int32_t n);",
+                "int syn_bad_struct(const syn_nowhere* s);", "int syn_bad_value(syn_step s);"):
+        with pytest.raises(_lib.SynHipError, match=re.search(r"syn_bad_\w+", bad).group()):
+            _lib.prototypes("int syn_good(int32_t n);\n" + bad)
 
 
 def test_c_abi_entry_points_reject_null_and_zero_arguments_without_crashing():
