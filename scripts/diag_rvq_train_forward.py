@@ -3,7 +3,7 @@
 the default 3 (W_hi x_hi + W_lo x_hi + W_hi x_lo), each against the fp32 restatement's autograd fed the run's own indices.  The backward is the
 same single-bf16 one in both.  Prints rec_pose's and every weight gradient's rel-L2 error per case, in backward order (last convolution first).
 
-    python scripts/diag_rvq_train_forward.py            # the fixture's two cases and (N 2, T 32, dim 180)
+    python scripts/diag_rvq_train_forward.py            # the fixture's two cases, (N 2, T 32, dim 180) and (N 8, T 256, dim 57: 512 latent rows)
 """
 import os
 import sys
@@ -13,7 +13,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from syntalker_amd import rvq_training, rvqvae, synth          # noqa: E402
 from tests import rvq_train_ref as ref                          # noqa: E402
-from tests.test_gpu_rvq_train import GOLDEN, STEP_CASES, make_draws, rel_l2, to_dev   # noqa: E402
+from tests.rvq_train_ref import make_draws                      # noqa: E402
+from tests.test_gpu_rvq_train import GOLDEN, STEP_CASES, rel_l2, to_dev   # noqa: E402
 
 DEV = "cuda"
 

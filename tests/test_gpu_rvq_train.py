@@ -7,7 +7,12 @@ Bounds: the quantiser is fp32 and a discrete decision - indices EQUAL, outputs 1
 (the gate tests/test_gpu_parity.py puts on bf16-operand gradients).  Measured values: DESIGN.md 16.5.
 Shapes: (N 3, T 16, dim 57) has 4 latent frames, fewer than the dilation of 9 - every non-centre tap of those convolutions reads padding and the
 weight gradient's shifted reads leave the clip - an odd N, and 12 rows < 512 codes (`_tile`'s repeat-and-noise branch); (2, 64, 78) runs with
-start = 2 (layers 3 .. 5 skipped); dims 57 / 78 / 180 are no multiples of 32 (padded lanes in the first weight gradient and the last data gradient)."""
+start = 2 (layers 3 .. 5 skipped); dims 57 / 78 / 180 are no multiples of 32 (padded lanes in the first weight gradient and the last data gradient);
+(8, 256, 57) has 512 latent rows, the first count at which `_tile` takes no noise, and K up to 2048.  The quantiser alone also runs at 511 / 512 /
+513 / 1030 rows (section 1b), where its indices are judged in fp64 along the kernel's own picks instead of being asked to equal an fp32 chain's.
+Draws the fixture does not hold come from `ref.make_draws`; every step asserts that its indices spread over more than one code per layer (an
+earlier version of the Gumbel expression was NaN everywhere and every row picked code 0: tests/test_rvq_train_host.py).
+The kernels one at a time, at far tighter bounds: tests/test_gpu_rvq_train_kernels.py."""
 import os
 
 import numpy as np
@@ -16,6 +21,7 @@ import torch
 
 from syntalker_amd import rvq_training, rvqvae, synth
 from tests import rvq_train_ref as ref
+from tests.rvq_train_ref import make_draws
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -30,16 +36,6 @@ def rel_l2(a, b):
 @pytest.fixture(scope="module")
 def fx():
     return ref.load_fixture(GOLDEN)
-
-
-def make_draws(n, t, start, seed, init):
-    """Draws for shapes the fixture does not hold, from a CPU generator."""
-    g = torch.Generator().manual_seed(seed)
-    rows, n_active = n * t // 4, 6 if start is None else start + 1
-    u = lambda *s: torch.rand(*s, generator=g).clamp_(1e-20, 1.0)
-    return {"gumbel": [-torch.log(-torch.log(u(rows, 512)).clamp_min(1e-20)) if q < n_active else None for q in range(6)],
-            "keep": [torch.rand(n, 512, tb, generator=g) >= 0.2 for tb in (t // 2,) * 3 + (t // 4,) * 6 + (t // 2,) * 3], "start": start,
-            "tile": [[torch.randn(512, 512, generator=g) for _ in range(1 if init[q] else 2)] if q < n_active and rows < 512 else [] for q in range(6)]}
 
 
 def to_dev(draws):
@@ -108,8 +104,104 @@ def test_quantiser_with_one_active_layer(fx):
     check_state(tr, 0, cbs[0], st["code_sum"][0], st["code_count"][0])
 
 
+# ---- 1b. the quantiser at the workload's row counts --------------------------------------------------------------------------------------
+# rows = N x T': 511 is the last shape on `_tile`'s noise side, 512 the first without noise (a null noise pointer, dead codes reset from row c of
+# the batch), 513 leaves a tail of one row in k_quantize_train<4> and makes k_code_update walk chunks of 256 + 256 + 1 rows, 1030 runs
+# k_quantize_train<16> with 6 clamped tail rows and sums sqerr over 65 groups.  Latent frames need no pose: `quantize` takes (N, T', 512).
+QUANT_SHAPES = {511: (7, 73), 512: (8, 64), 513: (9, 57), 1030: (5, 206)}
+
+
+@pytest.fixture(scope="module")
+def vq_sd():
+    return synth.synth_vq_state_dict(57)
+
+
+def check_quantiser_step(tr, vq_sd, rows, step, draws=None):
+    """One `RVQTrainer.quantize` from the trainer's current state.  The indices are judged in fp64 along the kernel's own picks
+    (ref.judge_picks / check_picks: "indices equal" cannot be asked of an fp32 distance chain over a thousand rows), everything else against
+    the restatement started from the same state and fed those picks."""
+    n, t4 = QUANT_SHAPES[rows]
+    init = list(tr.init)
+    cbs = [tr.model.get_buffer(f"quantizer.layers.{q}.codebook").cpu().clone() for q in range(6)]
+    code_sum, code_count = list(tr.code_sum.cpu().clone()), list(tr.code_count.cpu().clone())
+    lat = ref.quantiser_latents(vq_sd, n, t4, seed=3 + step)
+    draws = make_draws(n, 4 * t4, None, 50 + step, init, keep=False) if draws is None else draws
+    assert [len(z) for z in draws["tile"]] == [((1 if i else 2) if rows < 512 else 0) for i in init]
+    out = tr.quantize(lat.to(DEV), to_dev(draws))
+    idx = out["idx"].cpu().long()
+    assert out["n_active"] == 6 and int(idx.min()) >= 0 and int(idx.max()) < 512 and tr.init == [True] * 6
+    x = lat.reshape(-1, 512)
+    judged = ref.judge_picks(x, cbs, init, idx, draws["gumbel"], 6)
+    off = sum(int((idx[:, q] != j["argmax"]).sum()) for q, j in enumerate(judged))
+    share = ref.check_picks(judged, idx)
+    want = ref.quantiser_step_ref(lat, cbs, code_sum, code_count, init, draws, idx)
+    err_xq = float((out["xq"].cpu() - want["xq"]).abs().max())
+    commit, perp = float(out["commit"]), float(out["perplexity"])
+    print(f"{rows} rows, step {step}, init {init[0]}: near-tie share {share:.4f}, picks off the fp64 argmax {off} of {idx.numel()}, xq {err_xq:.2e}, "
+          f"commit {commit:.6e} (ref {float(want['commit']):.6e}), perplexity {perp:.4f} (ref {float(want['perplexity']):.4f})")
+    assert err_xq <= 1e-6
+    assert abs(commit - float(want["commit"])) <= 1e-4 and abs(perp - float(want["perplexity"])) <= 1e-3
+    inputs, resets = ref.layer_inputs(x, cbs, init, idx, 6), []
+    for q in range(6):
+        check_state(tr, q, want["codebooks"][q], want["code_sum"][q], want["code_count"][q])
+        assert torch.equal(tr._weights["bcount"][q].cpu(), torch.bincount(idx[:, q], minlength=512).float()), q
+        reset = tr.code_count[q].cpu() < 1.0
+        assert torch.equal(reset, want["code_count"][q] < 1.0), q
+        resets.append(int(reset.sum()))
+        if rows >= 512:                                                   # a dead code becomes row c of the layer's input, bit for bit: no noise term
+            assert torch.equal(tr.model.get_buffer(f"quantizer.layers.{q}.codebook").cpu()[reset], inputs[q][0][:512][reset]), q
+    print(f"    codes reset per layer {resets}, most rows on one code {[int(torch.bincount(idx[:, q]).max()) for q in range(6)]}")
+    return resets
+
+
+@pytest.mark.parametrize("rows", list(QUANT_SHAPES))
+def test_quantiser_at_workload_row_counts(vq_sd, rows):
+    """Two consecutive steps on two latent batches from an initialised EMA state in which a sixth of the codes sit below the usage threshold:
+    every layer quantises, updates and resets on both steps, and the second step's resets read rows that are not the codebook."""
+    tr = new_trainer(57)
+    sd = tr.state_dict()
+    sd["code_sum"], sd["code_count"] = ref.initialised_state(vq_sd)
+    sd["init"] = [True] * 6
+    tr.load_state_dict(sd)
+    for step in range(2):
+        resets = check_quantiser_step(tr, vq_sd, rows, step)
+        assert min(resets) > 50, resets
+
+
+def test_quantiser_first_step_at_513_rows(vq_sd):
+    """The reference's first step at >= 512 rows: layer 0's codebook is the first 512 rows of the batch, so those rows leave zero residuals
+    and the later layers initialise from them.  Kept, because it is what training does."""
+    tr = new_trainer(57)
+    check_quantiser_step(tr, vq_sd, 513, 0)
+
+
+def test_noise_boundary_and_the_trainers_own_draws(vq_sd):
+    """511 rows need `_tile`'s normals - leaving them out raises - and 512 rows take none; `RVQTrainer.draw` at 513 rows returns no normals and
+    finite Gumbel noise, on which the quantiser's picks hold up in fp64 as well."""
+    assert [len(z) for z in make_draws(7, 4 * 73, None, 1, [True] * 6, keep=False)["tile"]] == [1] * 6
+    assert [len(z) for z in make_draws(8, 4 * 64, None, 1, [False] * 6, keep=False)["tile"]] == [0] * 6
+    tr = new_trainer(57)
+    untouched = tr.model.get_buffer("quantizer.layers.0.codebook").clone()
+    draws = make_draws(7, 4 * 73, None, 1, [False] * 6, keep=False)
+    draws["tile"] = [[] for _ in range(6)]
+    with pytest.raises(ValueError):
+        tr.quantize(ref.quantiser_latents(vq_sd, 7, 73, seed=3).to(DEV), to_dev(draws))
+    assert tr.init == [False] * 6 and torch.equal(tr.model.get_buffer("quantizer.layers.0.codebook"), untouched)
+    n, t4 = QUANT_SHAPES[513]
+    own = tr.draw(n, 4 * t4, DEV)
+    assert [len(z) for z in own["tile"]] == [0] * 6 and len(own["keep"]) == 12
+    assert all(g is None or (tuple(g.shape) == (513, 512) and bool(torch.isfinite(g).all())) for g in own["gumbel"])
+    own = {"gumbel": [torch.empty(513, 512, device=DEV).exponential_().log_().neg_().cpu() if g is None else g.cpu() for g in own["gumbel"]],
+           "start": None, "tile": own["tile"], "keep": []}               # (a quantise-dropout draw would skip layers: judge all six)
+    assert all(bool(torch.isfinite(g).all()) for g in own["gumbel"])
+    check_quantiser_step(tr, vq_sd, 513, 0, draws=own)
+
+
 # ---- 2, 3. forward and backward with injected draws --------------------------------------------------------------------------------------
-STEP_CASES = {"n3_t16_dim57": (0, None), "n2_t64_dim78_start2": (1, None), "n2_t32_dim180": (None, (2, 32, 180, "hands", None))}
+# the last case is the first shape on the workload's side of `_tile`: 512 latent rows (no noise, resets from the batch's own rows) and
+# K = 2048 / 1024 / 512 positions per weight gradient
+STEP_CASES = {"n3_t16_dim57": (0, None), "n2_t64_dim78_start2": (1, None), "n2_t32_dim180": (None, (2, 32, 180, "hands", None)),
+              "n8_t256_dim57": (None, (8, 256, 57, "lower_trans", None))}
 
 
 @pytest.fixture(scope="module")
@@ -128,6 +220,9 @@ def step_results(fx):
         got = tr.forward_backward(pose.to(DEV), to_dev(draws))
         hip = {"rec_pose": got["rec_pose"].cpu(), "idx": got["idx"].cpu().long(), "grads": {k: v.cpu().clone() for k, v in got["grads"].items()},
                "scalars": [float(got[k]) for k in ("loss", "recons", "commit", "perplexity")]}
+        used = [int(hip["idx"][:, q].unique().numel()) for q in range(got["n_active"])]
+        print(f"{name}: distinct codes per active layer {used}")
+        assert min(used) > 1, (name, used)                                # a step whose every row picks one code checks next to nothing
         want = ref.train_step(synth.synth_vq_state_dict(dim), ref.new_state(), pose, draws, forced_idx=hip["idx"])
         out[name] = (hip, want, case)
     return out

@@ -164,3 +164,89 @@ def test_body_part_masks_have_the_reference_widths():
     assert lt[:8] == [0, 1, 2, 3, 619, 620, 621, 622] and lt[8:11] == [4 + 459, 4 + 459 + 1, 4 + 459 + 2]      # joint 0: velocity only
     with pytest.raises(ValueError):
         rvq_training.body_part_mask("whole")
+
+
+# ---- the draws the GPU suite injects, and how sharp its comparisons are ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(2, 32, None), (3, 16, None)])
+def test_made_draws_are_gumbel_noise_and_spread_the_picks(shape):
+    """`make_draws` once wrote -log(-log(u).clamp_min(1e-20)): the clamp bound to log(u) <= 0, every element came out NaN, argmax picked code 0
+    for every row of every layer and the kernel agreed.  Gumbel noise is finite and has mean 0.5772 (Euler's constant; an (N T / 4) x 512
+    draw has a standard error below 0.02), and a step on it uses more than one code in every active layer."""
+    n, t, start = shape
+    draws = ref.make_draws(n, t, start, 17, [False] * 6)
+    for g in draws["gumbel"]:
+        assert g.shape == (n * t // 4, 512) and bool(torch.isfinite(g).all())
+        assert abs(float(g.double().mean()) - 0.5772) <= 0.05
+    assert [len(z) for z in draws["tile"]] == [2] * 6 and [tuple(k.shape) for k in draws["keep"][:4]] == [(n, 512, t // 2)] * 3 + [(n, 512, t // 4)]
+    out = ref.train_step(synth.synth_vq_state_dict(57), ref.new_state(), synth.synth_vq_pose("lower", 57, n=n, t=t, seed=3), draws, with_grads=False)
+    used = [int(out["idx"][:, q].unique().numel()) for q in range(out["n_active"])]
+    print(f"{shape}: distinct codes per layer {used}")
+    assert out["n_active"] == 6 and min(used) > 1, used
+
+
+def test_wgrad_comparison_sees_each_wrong_read():
+    """tests/test_gpu_rvq_train_kernels.py holds k_wgrad to 2 K 2^-24 sum |dy x| per element against fp64 on WGRAD_CASES.  Four wrong kernels,
+    applied to that fp64 reference instead of being built: a tap shift that ignores the dilation, a read that ignores the clip boundary, a
+    dropped `>> up`, a partial chunk's last position left out.  Every case a mutation can touch must put some element over its bound; the
+    distances, in units of the bound, are in DESIGN.md 16.5."""
+    def strays(case):
+        """Some shifted read leaves its clip and still lands inside the buffer (one-frame clips under dilation 9 leave the buffer altogether)."""
+        taps, stride, dil, pad, up, _ = ref.WGRAD_GEOMETRY[case[0]]
+        clips, t_out = case[5], case[6]
+        t_in = t_out * stride if not up else t_out // 2
+        return any(not 0 <= t * stride + tap * dil - pad < (t_in << up) and 0 <= n * t_in + ((t * stride + tap * dil - pad) >> up) < clips * t_in
+                   for n in range(clips) for t in range(t_out) for tap in range(taps))
+
+    touches = {"dilation": lambda c: ref.WGRAD_GEOMETRY[c[0]][2] > 1, "clip": strays,
+               "up": lambda c: ref.WGRAD_GEOMETRY[c[0]][4] == 1, "last": lambda c: c[5] * c[6] % 64 != 0}
+    worst, seen = {m: float("inf") for m in touches}, {m: set() for m in touches}
+    for case in ref.WGRAD_CASES:
+        geo, cout, _, cin, _, clips, t_out = case
+        if cout * cin * clips * t_out > 128 * 192 * 130:                  # the 512-channel twins of a small case add nothing here
+            continue
+        dy, x, _ = ref.wgrad_operands(case)
+        args = (dy[..., :cout], x[..., :cin]) + ref.WGRAD_GEOMETRY[geo]
+        want, mag, _, _ = ref.wgrad_ref(*args)
+        bound = ref.wgrad_bound(mag, clips * t_out)
+        for m, applies in touches.items():
+            if not applies(case):
+                continue
+            got = ref.wgrad_ref(*args, mutate=m)[0]
+            over = (got - want).abs() > bound
+            assert bool(over.any()), (m, case)
+            ratio = float(((got - want).abs()[over] / bound[over].clamp_min(1e-300)).max())
+            worst[m], _ = min(worst[m], ratio), seen[m].add(geo)
+    print("smallest of the per-case largest |mutant - right| / bound:", {m: f"{v:.3g}" for m, v in worst.items()})
+    assert seen["dilation"] == {"dil3", "dil9"} and seen["up"] == {"up"} and seen["clip"] == set(ref.WGRAD_GEOMETRY) - {"k1"}
+    assert seen["last"] == set(ref.WGRAD_GEOMETRY)                        # every geometry meets a partial last chunk
+    for geo in ref.WGRAD_GEOMETRY:                                        # ... an odd K (`up` has an even t_out) and several chunks with a partial tail
+        ks = {c[5] * c[6] for c in ref.WGRAD_CASES if c[0] == geo}
+        assert any(k > 64 and k % 64 for k in ks) and (geo == "up" or any(k % 2 for k in ks)), (geo, ks)
+    # dilation 9 on clips of one frame: every off-centre tap reads padding, the gradient there is exactly zero with a zero bound
+    case = next(c for c in ref.WGRAD_CASES if c[0] == "dil9" and c[6] == 1)
+    dy, x, _ = ref.wgrad_operands(case)
+    want, mag, _, _ = ref.wgrad_ref(dy[..., :case[1]], x[..., :case[3]], *ref.WGRAD_GEOMETRY["dil9"])
+    assert float(mag[:, :, [0, 2]].max()) == 0.0 and float(want[:, :, [0, 2]].abs().max()) == 0.0 and float(mag[:, :, 1].median()) > 0.0
+
+
+def test_code_update_comparison_sees_a_lost_chunk_and_stray_noise():
+    """The quantiser tests at 512 rows and more hold code_sum / code_count / codebook to 1e-5 and the reset rows to bit equality.  Two wrong
+    kernels, applied to the restatement: the second 256-row chunk of the per-code sums left out, `_tile`'s noise added to the reset rows."""
+    sd = synth.synth_vq_state_dict(57)
+    cbs = [sd[f"quantizer.layers.{q}.codebook"].float() for q in range(6)]
+    code_sum, code_count = ref.initialised_state(sd)
+    lat = ref.quantiser_latents(sd, 9, 57, seed=3)
+    draws = ref.make_draws(9, 4 * 57, None, 50, [True] * 6, keep=False)
+    idx = ref.residual_vq([c.clone() for c in cbs], {"init": [True] * 6, "code_sum": list(code_sum.clone()), "code_count": list(code_count.clone())},
+                          lat.permute(0, 2, 1).clone(), draws)[1]
+    run = lambda m: ref.quantiser_step_ref(lat, cbs, list(code_sum), list(code_count), [True] * 6, draws, idx, mutate=m)
+    want, same, chunk, noise = run(None), run("same"), run("second_chunk"), run("noise")
+    dist = lambda a, k: min(float((a[k][q] - want[k][q]).abs().max()) for q in range(6)) / 1e-5
+    assert max(dist(same, k) for k in ("codebooks", "code_sum", "code_count")) == 0.0     # the re-written update IS the restatement's
+    print("in units of the 1e-5 bound, smallest over the layers: lost chunk", {k: f"{dist(chunk, k):.3g}" for k in ("code_sum", "code_count")},
+          "stray noise", f"{dist(noise, 'codebooks'):.3g}")
+    assert dist(chunk, "code_sum") > 1 and dist(chunk, "code_count") > 1 and dist(noise, "codebooks") > 1
+    for q in range(6):
+        reset = want["code_count"][q] < 1
+        x = ref.layer_inputs(lat.reshape(-1, 512), cbs, [True] * 6, idx, 6)[q][0]
+        assert int(reset.sum()) > 50 and torch.equal(want["codebooks"][q][reset], x[:512][reset]) and not torch.equal(noise["codebooks"][q][reset], x[:512][reset])
