@@ -314,6 +314,42 @@ int syn_mesh_vertices(const float* dirs_packed, int32_t n_verts, int32_t kc, con
 int64_t syn_vertex_losses_workspace_bytes(int64_t n, int32_t channels);
 int syn_vertex_losses(const float* rec, const float* tar, int64_t n, int32_t channels, void* workspace, int32_t blocks, double* out, void* stream);
 
+/* Drawing the mesh: the scene of the reference's utils/fast_render.py:16-43 (one mesh, one orthographic camera, one directional light, one uniform
+ * colour) as a software rasteriser in three stages (additive, SYN_ABI_VERSION stays 9; csrc/syn_render.inc).  Every call enqueues on
+ * `stream`, allocates nothing, is graph-capturable, deterministic and uses no atomics of any kind; a frame's output is bitwise the same whichever frames
+ * share the call.  width, height: 1 .. 8192 pixels, row 0 on top.  faces (n_faces, 3) int32 vertex indices; a face with an index outside
+ * [0, n_verts) is skipped by every stage.
+ *
+ * syn_render_project: vertices (n_frames, n_verts, 3) in world space, view_3x4 = the first three rows of the inverse camera pose (12 floats on the
+ * device) ->
+ *   xy_sub (n_frames, n_verts, 2) int32   rint(16 x_pix), rint(16 y_pix): x_pix = W/2 + x_cam (H/2)/ymag, y_pix = H/2 - y_cam (H/2)/ymag (square
+ *                                         pixels, ymag spans half the height); INT32_MIN, INT32_MIN for a vertex that is not finite; finite positions
+ *                                         are clamped to +-2^30
+ *   z (n_frames, n_verts)                 -z_cam, the distance in front of the camera
+ *   normal (n_frames, n_verts, 3)         normalise(sum (p1 - p0) x (p2 - p0)) over the vertex's faces in ascending face index (zero for a zero sum),
+ *                                         in world space.  vf_offsets (n_verts + 1), vf_faces (n_incident): the vertex -> faces CSR index, built once
+ *                                         on the host.  Faces with a vertex that is not finite are left out of the sum.
+ * syn_render_raster: -> face_id (n_frames, height, width) int32 (-1: background), depth (n_frames, height, width) fp32 (+inf: background).  The sample
+ * of pixel (i, j) is (16 i + 8, 16 j + 8) in xy_sub's units.  A face is oriented to a positive doubled area A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0)
+ * (vertices 1 and 2 swap otherwise); with E_ab(p) = (bx - ax)(py - ay) - (by - ay)(px - ax), w0 = E_12, w1 = E_20, w2 = E_01 in int64, a sample is
+ * covered when every w > 0, or = 0 on a top (dy = 0, dx > 0) or left (dy < 0) edge.  Dropped whole: faces of zero area, with a sentinel vertex, or with
+ * a vertex more than 16 max(width, height) units (one image side) outside a border; faces partly outside the image are clipped by the pixel loop.
+ * Depth = ((w0 z0 + w1 z1) + w2 z2) / A in fp32, w and A converted from their integers, every operation rounded on its own; a fragment outside
+ * [znear, zfar] is rejected; the nearer fragment wins, on equal depth the lower face index.  workspace: syn_render_workspace_bytes(n_frames, n_faces)
+ * bytes (-1 for counts below 1), 16-byte aligned; xy_sub 8-byte aligned.
+ * syn_render_shade: -> rgb (n_frames, height, width, 3) bytes.  Covered pixel: b = w / A, n = normalise((b0 n0 + b1 n1) + b2 n2), c = base *
+ * min(1, ambient + diffuse * max(0, n . light)), channel = rint(255 c); light = the unit vector towards the light, world space; no culling, no normal
+ * flip.  Other pixels: the background bytes.  A Lambert term of this project's own, not pyrender's shader. */
+int64_t syn_render_workspace_bytes(int64_t n_frames, int32_t n_faces);
+int syn_render_project(const float* vertices, int64_t n_frames, int32_t n_verts, const float* view_3x4, int32_t width, int32_t height, float ymag,
+                       const int32_t* faces, int32_t n_faces, const int32_t* vf_offsets, const int32_t* vf_faces, int32_t n_incident, int32_t* xy_sub,
+                       float* z, float* normal, void* stream);
+int syn_render_raster(const int32_t* xy_sub, const float* z, int64_t n_frames, int32_t n_verts, const int32_t* faces, int32_t n_faces, int32_t width,
+                      int32_t height, float znear, float zfar, void* workspace, int32_t* face_id, float* depth, void* stream);
+int syn_render_shade(const int32_t* face_id, const int32_t* xy_sub, const float* normal, int64_t n_frames, int32_t n_verts, const int32_t* faces,
+                     int32_t n_faces, int32_t width, int32_t height, float light_x, float light_y, float light_z, float base_r, float base_g, float base_b,
+                     float ambient, float diffuse, int32_t background_r, int32_t background_g, int32_t background_b, uint8_t* rgb, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

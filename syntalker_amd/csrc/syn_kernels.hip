@@ -1804,6 +1804,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_guide.inc"
 #include "syn_joints.inc"
 #include "syn_mesh.inc"
+#include "syn_render.inc"
 
 namespace {
 
