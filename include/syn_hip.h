@@ -350,6 +350,36 @@ int syn_render_shade(const int32_t* face_id, const int32_t* xy_sub, const float*
                      int32_t n_faces, int32_t width, int32_t height, float light_x, float light_y, float light_z, float base_r, float base_g, float base_b,
                      float ambient, float diffuse, int32_t background_r, int32_t background_g, int32_t background_b, uint8_t* rgb, void* stream);
 
+/* The audio front end: amplitude envelope and onset detection of 16 kHz waveforms (additive, SYN_ABI_VERSION stays 9; csrc/syn_audio.inc) -
+ * what dataloaders/beat_sep_lower.py:391-409 and utils/metric.py:64-76 take from numpy stride tricks and librosa.onset.onset_detect.  Several takes of
+ * different lengths share a call: y [total samples] fp32 is the takes back to back, sample_off and frame_off [n_takes + 1] int64 ON THE DEVICE are
+ * their first sample and first frame (take i: n_i samples, T_i = 1 + n_i / hop frames); max_samples / max_frames = the longest take's, total_frames =
+ * frame_off[n_takes].  Every call enqueues on `stream`, allocates nothing, uses no atomics; all arithmetic behind the samples is fp64 in a fixed order,
+ * and a take's result is bitwise the same whichever takes share the call.
+ *
+ * syn_audio_amplitude: out [total samples] fp32, per take a[i] = max |y[i .. i + frame_length)| for i <= n - frame_length, the last frame_length - 1
+ *   entries repeat a[n - frame_length]; frame_length 1 .. 4096; a take shorter than frame_length is left unwritten.
+ * syn_audio_power_spectrum: power [total_frames][1025] fp64 = |DFT_2048 of the Hann-windowed (periodic) frame ypad[t hop .. t hop + 2048)|^2, ypad = y
+ *   between 1024 zeros; hop 1 .. 2048.  A GEMM against the [cos | -sin] basis on v_mfma_f64_16x16x4_f64, angles reduced as integers (jk mod 2048).
+ * syn_audio_mel_db: mel_db [total_frames][128] fp64 = max(S, max over the take of S - 80), S = 10 log10(max(1e-10, Slaney mel filterbank (128 bands,
+ *   0 .. sr / 2) . power)); workspace: syn_audio_workspace_bytes(total_frames) bytes (-1 for a count below 1), 8-byte aligned - it holds `power`.
+ * syn_audio_onset_env: env [total_frames] fp64, env[t] = 0 for t < lag, else the mean over the bands (summed in ascending band order) of
+ *   max(0, mel_db[t - lag + 1] - mel_db[t - lag]), lag = 1 + 2048 / (2 hop) (the difference's lag plus librosa's centring shift; 3 at hop 512); env_norm = (env - min) / ((max - min) + FLT_MIN), min and max over the take.
+ * syn_audio_peak_pick: mask [total_frames] uint8, count [n_takes] int32.  Frame i of a take is an onset iff x[i] is the maximum of
+ *   x[max(0, i - pre_max) .. min(T, i + post_max)), x[i] >= delta + the mean of x[max(0, i - pre_avg) .. min(T, i + post_avg)) (summed in ascending
+ *   order, divided by the truncated window's length), and the previous onset is more than `wait` frames back (frames taken in order).  env_raw (may be
+ *   NULL): a take whose env_raw is zero everywhere has no onsets. */
+int64_t syn_audio_workspace_bytes(int64_t total_frames);
+int syn_audio_amplitude(const float* y, const int64_t* sample_off, int32_t n_takes, int64_t max_samples, int32_t frame_length, float* out, void* stream);
+int syn_audio_power_spectrum(const float* y, const int64_t* sample_off, const int64_t* frame_off, int32_t n_takes, int64_t max_frames, int64_t total_frames,
+                             int32_t hop, double* power, void* stream);
+int syn_audio_mel_db(const float* y, const int64_t* sample_off, const int64_t* frame_off, int32_t n_takes, int64_t max_frames, int64_t total_frames, double sr,
+                     int32_t hop, void* workspace, double* mel_db, void* stream);
+int syn_audio_onset_env(const double* mel_db, const int64_t* frame_off, int32_t n_takes, int64_t max_frames, int32_t hop, double* env, double* env_norm,
+                        void* stream);
+int syn_audio_peak_pick(const double* x, const double* env_raw, const int64_t* frame_off, int32_t n_takes, int32_t pre_max, int32_t post_max, int32_t pre_avg,
+                        int32_t post_avg, int32_t wait, double delta, uint8_t* mask, int32_t* count, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).

@@ -2,15 +2,18 @@
 """L1 diversity and beat consistency of a results directory as the reference's `test()` writes it (diffusion_rvqvae_trainer.py:702-709:
 `res_<id>.npz` with `poses` (n, 165) SMPL-X axis-angle, `trans`, `betas`), the way `test()` computes them (:626-638, 668, 677-684, 722-728).
 
-    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR] [--face]
+    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR | --waves DIR] [--face]
 
 Per take: rest joints and the hands' mean pose from the model file and the take's betas (joints.smplx_rest_joints, host), the 55 skeleton joints by
 forward kinematics on the device with zero transl as `test()` passes it (joints.smplx_joints; the hand mean pose is added to the hand joints'
 axis-angle vectors, as smplx does for the reference's model, built without flat_hand_mean), L1div.run on them, and - with --onsets - the beat
-consistency of the slice [mask, n - mask) against the take's audio onsets.
+consistency of the slice [mask, n - mask) against the take's audio onsets (with --waves: found on the device from the take's 16 kHz waveform).
 --mean-vel   the reference's `avg_vel` (55,): data_path + weights/mean_vel_<pose_rep>.npy
 --onsets     a directory with `<id>.npy`: onset times in seconds (what alignment.load_audio returns for the take's audio cut to the slice,
              librosa.onset.onset_detect); a take without its file, or with no onsets, is left out of `bc` (named on stderr)
+--waves      a directory with `<id>.wav` (or `<id>.npy`): the take's waveform at --audio-sr (16000: the reference's wave16k/), from which the onsets are
+             detected as test() does (:681-683; metrics.beat_consistency_from_audio, syntalker_amd.audio - no librosa).  A file at another rate is
+             refused: resampling is out of scope.  --onsets and --waves together are an error; with neither there is no `bc`
 --flat-hand-mean   for results made with a model built with flat_hand_mean=True: no hand mean pose is added
 --face       also test()'s `l2 loss` and `lvel loss` (:640-675, :713-714): the face meshes of `res_<id>.npz` against `gt_<id>.npz` (jaw pose and
              `expressions` of each, everything else zero; metrics.face_losses), accumulated as test() does: sum(value x n) / frames
@@ -28,7 +31,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from syntalker_amd import joints, mesh, metrics  # noqa: E402
+from syntalker_amd import audio, joints, mesh, metrics  # noqa: E402
 
 
 def read_ids(results_dir: str):
@@ -41,12 +44,16 @@ def main(argv=None):
     ap.add_argument("--smplx-model", required=True)
     ap.add_argument("--mean-vel", required=True)
     ap.add_argument("--onsets")
+    ap.add_argument("--waves")
+    ap.add_argument("--audio-sr", type=int, default=16000)
     ap.add_argument("--flat-hand-mean", action="store_true")
     ap.add_argument("--face", action="store_true")
     ap.add_argument("--mask", type=int, default=60)
     ap.add_argument("--sigma", type=float, default=0.3)
     ap.add_argument("--order", type=int, default=7)
     a = ap.parse_args(argv)
+    if a.onsets is not None and a.waves is not None:
+        ap.error("--onsets and --waves exclude each other: the onsets are read, or detected from the waveforms")
     ids = read_ids(a.results_dir)
     if not ids:
         raise SystemExit(f"motion_metrics_from_results: no res_<id>.npz in {a.results_dir}")
@@ -71,10 +78,17 @@ def main(argv=None):
                                            to_dev(gt["expressions"]).reshape(n, -1))
             l2_all += l2 * n
             lvel_all += lvel * n
-        if a.onsets is None:
+        if a.onsets is None and a.waves is None:
             continue
-        path = os.path.join(a.onsets, f"{i}.npy")
-        onsets = np.load(path).reshape(-1) if os.path.exists(path) else np.zeros(0)
+        if a.waves is not None:
+            path = next((p for p in (os.path.join(a.waves, f"{i}.wav"), os.path.join(a.waves, f"{i}.npy")) if os.path.exists(p)), None)
+            onsets = np.zeros(0)
+            if path is not None and n > 2 * a.mask:
+                short = metrics.audio_slice_of_test(audio.read_wave(path, a.audio_sr), n, a.mask, a.audio_sr, 30.0)
+                onsets = audio.onset_detect(short, sr=a.audio_sr, hop_length=512, units="time") if len(short) else onsets
+        else:
+            path = os.path.join(a.onsets, f"{i}.npy")
+            onsets = np.load(path).reshape(-1) if os.path.exists(path) else np.zeros(0)
         if onsets.size == 0 or n <= 2 * a.mask:
             print(f"motion_metrics_from_results: {i} has no onsets (or is not longer than twice the mask), left out of bc", file=sys.stderr)
             continue
@@ -82,7 +96,7 @@ def main(argv=None):
         bc_frames += n - 2 * a.mask
         bc_takes += 1
     out = {"takes": len(ids), "frames": int(frames), "l1div": l1.avg()}
-    if a.onsets is not None:
+    if a.onsets is not None or a.waves is not None:
         out.update({"bc": align / bc_frames if bc_frames else None, "bc_takes": bc_takes, "bc_frames": int(bc_frames)})
     if a.face:
         out.update({"l2": l2_all / frames, "lvel": lvel_all / frames})

@@ -370,7 +370,7 @@ def beat_align(mask, onset_times, upper_body=UPPER_BODY, pose_fps: float = 30.0,
 
 class alignment(object):
     """utils/metric.py:54-241 with the reference's signatures.  `load_pose` and `calculate_align` run on the device; `load_audio` is librosa's
-    onset detector and nothing else, so it stays librosa's (imported when called)."""
+    onset detector and nothing else, so it stays librosa's (imported when called); `load_audio_hip` is the same call on this package's detector."""
 
     def __init__(self, sigma, order, mmae=None, upper_body=[3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21]):
         self.sigma = sigma
@@ -389,6 +389,15 @@ class alignment(object):
         y = wave if without_file else librosa.load(wave)[0]
         short_y = y if t_start is None else y[t_start:t_end]
         return librosa.onset.onset_detect(y=short_y, sr=sr_audio, hop_length=512, units="time")
+
+    def load_audio_hip(self, wave, t_start=None, t_end=None, without_file=False, sr_audio=16000):
+        """`load_audio` on this package's onset detector (syntalker_amd.audio, csrc/syn_audio.inc) instead of librosa's: the onset times in seconds of
+        wave[t_start:t_end] as a float64 numpy array.  `wave`: the waveform at `sr_audio` (without_file=True, as test() calls it), or a `.wav` / `.npy`
+        file AT that rate - the reference's `librosa.load` resamples a file to 22.05 kHz and detects at `sr_audio` all the same; this does not."""
+        from . import audio
+        y = wave if without_file else audio.read_wave(wave, sr_audio)
+        short_y = y if t_start is None else y[t_start:t_end]
+        return np.asarray(audio.onset_detect(short_y, sr=sr_audio, hop_length=512, units="time"), dtype=np.float64)
 
     def load_pose(self, pose, t_start, t_end, pose_fps, without_file=False):
         """pose (n, J * 3) joints -> one array of beat indices (slice indices) per joint."""
@@ -439,6 +448,33 @@ def beat_consistency(joints, onset_times, mmae, align_mask: int = 60, sigma: flo
     n = vel.shape[-2]
     mask = motion_beat_mask(vel, align_mask, n - align_mask, order, threshold)
     return beat_align(mask, onset_times, upper_body, pose_fps, sigma)[1]
+
+
+def audio_slice_of_test(wave, n_frames: int, align_mask: int = 60, audio_sr=16000, pose_fps: float = 30.0):
+    """The stretch of a take's waveform `test()` detects onsets on (diffusion_rvqvae_trainer.py:681-683), as written there: the wave is cropped to
+    int(audio_sr / pose_fps * n) samples, and of THAT the slice [a_offset : len(wave) - a_offset] is taken, a_offset = int(align_mask * (audio_sr /
+    pose_fps)) - the end of the slice is counted from the end of the UNCROPPED wave, so it cuts into the crop only where the file is less than
+    a_offset samples longer than the motion."""
+    a_offset = int(align_mask * (audio_sr / pose_fps))
+    return wave[:int(audio_sr / pose_fps * n_frames)][a_offset:len(wave) - a_offset]
+
+
+def beat_consistency_from_audio(joints, wave, mmae, align_mask: int = 60, sigma: float = 0.3, order: int = 7, upper_body=UPPER_BODY, threshold: float = 0.3,
+                                audio_sr=16000, pose_fps: float = 30.0):
+    """`beat_consistency` of one take from its waveform at `audio_sr` (1-D: numpy, CPU or device tensor) instead of onset times: the onsets are those of
+    `audio_slice_of_test(wave, n)` by syntalker_amd.audio.onset_detect (hop 512, units 'time') - lines 681-684 of the reference's test() on a machine
+    without librosa.  A slice without onsets is a ValueError, as in `beat_align`."""
+    from . import audio
+    shape = tuple(joints.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"beat_consistency_from_audio: one take of joints, (n, J * 3) or (n, J, 3), got {shape}")
+    if len(tuple(wave.shape)) != 1:
+        raise ValueError(f"beat_consistency_from_audio: the waveform is 1-D, got {tuple(wave.shape)}")
+    short = audio_slice_of_test(wave, shape[0], align_mask, audio_sr, pose_fps)
+    if len(short) == 0:
+        raise ValueError("beat_consistency_from_audio: the take's audio slice is empty (no onsets)")
+    onsets = audio.onset_detect(short, sr=audio_sr, hop_length=512, units="time")
+    return beat_consistency(joints, onsets, mmae, align_mask=align_mask, sigma=sigma, order=order, upper_body=upper_body, pose_fps=pose_fps, threshold=threshold)
 
 
 # ---- the face numbers of test(): `l2 loss` and `lvel loss` over the face meshes (diffusion_rvqvae_trainer.py:640-675) -----------------------------
