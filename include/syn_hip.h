@@ -380,6 +380,51 @@ int syn_audio_onset_env(const double* mel_db, const int64_t* frame_off, int32_t 
 int syn_audio_peak_pick(const double* x, const double* env_raw, const int64_t* frame_off, int32_t n_takes, int32_t pre_max, int32_t post_max, int32_t pre_avg,
                         int32_t post_avg, int32_t wait, double delta, uint8_t* mask, int32_t* count, void* stream);
 
+/* Baseline JPEG of device frames (additive, SYN_ABI_VERSION stays 9; csrc/syn_jpeg.inc): what the reference's utils/media.py hands to
+ * ffmpeg frame by frame is encoded where syn_render_shade left it, so that a picture crosses to the host as a file of a fiftieth of its size.  Every
+ * call enqueues on `stream`, allocates nothing and uses no atomics.  Nothing is floating point: a frame's bytes are those of the numpy restatement
+ * (tests/jpeg_ref.py) and do not depend on its batch mates, on how a take is cut into calls, or on the launch geometry.
+ *
+ * Input    rgb: n_frames pictures of (height, width, 3) bytes, R G B, rows top down, densely packed, frame_stride bytes apart (>= 3 width height);
+ *          width, height 1 .. 8192.
+ * Padding  to multiples of 16 (W16, H16) by repeating the last column and row.
+ * Colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *          Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *          Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16            (arithmetic shifts)
+ * Chroma   4:2:0: (a + b + c + d + 2) >> 2 over each 2 x 2.        Level shift: s = p - 128.
+ * DCT      M[u][x] = rint(8192 * 1/2 * c(u) * cos((2x + 1) u pi / 16)), c(0) = 1/sqrt 2, else 1: 64 integer constants in the source.
+ *          T = (S M^T + 1024) >> 11 (arithmetic), F = M T: the DCT scaled by 2^15.  All of it is int32: a row of M sums to at most 23168 in absolute
+ *          value (row 0), so |S M^T| <= 128 * 23168 < 3.0e6, |T| <= 1448, |F| <= 1448 * 23168 < 3.4e7, and |F| + (Q << 14) < 3.8e7.
+ * Quantise q = sign(F) * ((|F| + (Q << 14)) / (Q << 15)), an integer division; |q| <= 1024.
+ * Tables   Q = clamp((base * s + 50) / 100, 1, 255), base = the luminance / chrominance table of ITU T.81 Annex K.1, s = 5000 / quality below
+ *          quality 50, else 200 - 2 quality (the IJG rule); quality 1 .. 100.
+ * Entropy  baseline sequential, the four Huffman tables of Annex K.3, one interleaved scan, MCU = Y00 Y01 Y10 Y11 Cb Cr, zigzag order.  The restart
+ *          interval is one MCU row (DRI = W16 / 16): the DC prediction starts from 0 in every interval, the interval's last byte is filled with
+ *          1-bits, 0xFF is followed by 0x00 inside entropy data, intervals are joined by RST(row & 7).  That makes the rows independent work.
+ * File     SOI, JFIF APP0, two DQT, SOF0 (8 bit, height, width, components 0x22 / 0x11 / 0x11), four DHT, DRI, SOS, data, EOI.  Everything in
+ *          front of the data is constant per width, height and quality; the caller passes it (syntalker_amd/video.py jpeg_header).
+ *
+ * Capacity: count first, write second.  No stage writes by a guessed size.  syn_jpeg_measure runs the entropy coder without storing a byte and
+ * leaves every interval's exact size; syn_jpeg_write runs the same code again and stores each interval at the place the sizes give it.  A `data` of
+ * fewer than offsets[n_frames] bytes is left untouched, every store of an interval is held below its counted size, and an interval whose place
+ * does not lie inside data[0 .. capacity) is skipped: whatever the workspace holds, syn_jpeg_write stores nowhere else.  Inside the coder a block
+ * has a fixed region of 53 words, above the proven bound: a block codes to at most 20 + 63 * 26 = 1658 bits = 52 words before stuffing (the coder
+ * clamps a DC difference to +-2047 and an AC coefficient to +-1023, which the transform never exceeds, so the bound holds for any input).
+ *
+ * workspace: syn_jpeg_workspace_bytes(n_frames, width, height) bytes (-1 for a count below 1 or a size out of range), 16-byte aligned: the quantised
+ * coefficients (int16, 768 bytes per MCU, scan order), the interval sizes and their places.  The three calls of a batch share it, in this order:
+ * syn_jpeg_transform  rgb -> the coefficients.
+ * syn_jpeg_measure    -> offsets (n_frames + 1) int64 on the device: frame k will occupy data[offsets[k] .. offsets[k + 1]), a complete file with
+ *                     header_bytes of header in front.
+ * syn_jpeg_write      -> data (capacity >= offsets[n_frames] bytes, which the caller has read back): header (header_bytes on the device), intervals,
+ *                     RST markers and EOI of every frame.  offsets as syn_jpeg_measure left them. */
+int64_t syn_jpeg_workspace_bytes(int64_t n_frames, int32_t width, int32_t height);
+int syn_jpeg_transform(const uint8_t* rgb, int64_t frame_stride, int64_t n_frames, int32_t width, int32_t height, int32_t quality, void* workspace,
+                       void* stream);
+int syn_jpeg_measure(int64_t n_frames, int32_t width, int32_t height, int32_t header_bytes, void* workspace, int64_t* offsets, void* stream);
+int syn_jpeg_write(int64_t n_frames, int32_t width, int32_t height, const uint8_t* header, int32_t header_bytes, const void* workspace,
+                   const int64_t* offsets, uint8_t* data, int64_t capacity, void* stream);
+
 /* n_steps consecutive steps of a hook-free stretch of p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:714-739,
  * 905-931), in place (x_next = x_t): step j takes its timesteps from t_model + j * t_model_stride and
  * t_coef + j * t_coef_stride (the rows syn_steps_advance fills), its noise from rng (noise must be NULL when n_steps > 1).
