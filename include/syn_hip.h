@@ -380,6 +380,29 @@ int syn_audio_onset_env(const double* mel_db, const int64_t* frame_off, int32_t 
 int syn_audio_peak_pick(const double* x, const double* env_raw, const int64_t* frame_off, int32_t n_takes, int32_t pre_max, int32_t post_max, int32_t pre_avg,
                         int32_t post_avg, int32_t wait, double delta, uint8_t* mask, int32_t* count, void* stream);
 
+/* Audio resampling (additive, SYN_ABI_VERSION stays 9; csrc/syn_audio_resample.inc): a waveform from any integer rate to any other, what
+ * the reference takes from librosa.load + librosa.resample (dataloaders/beat_sep_lower.py:392-393, diffusion_rvqvae_trainer.py:679-680).  Band-limited
+ * interpolation with a Kaiser-windowed sinc on the exact rational grid: with up / down = target rate / source rate in lowest terms (a common factor is
+ * refused) a take of n samples becomes ceil(n up / down) samples,
+ *   out[m] = sum_j y[j] h[m down - j up],  y zero outside the take,  h[k] = 0 for |k| > K,
+ * each sum one fp64 fma chain over ASCENDING j from 0.0; out64 receives the sum, out32 the sum rounded once to fp32.  Either may be NULL, not both.
+ *
+ * Takes as above: y [total samples] fp32 back to back, sample_off and out_off [n_takes + 1] int64 ON THE DEVICE, the first sample of take i in y and
+ * its first output in out32 / out64 (out_off[n_takes] is not read); max_samples = the longest take's samples (it sizes the grid; 1 .. 2^46 / up).
+ * taps [n_taps] fp64 on the device, 16-byte aligned, is h in PAIRS, tap-major over the outputs' residues: with W = K / up (integer division) and
+ * T = 2 W + 2, n_taps = T up and
+ *   taps[((t / 2) up + r) 2 + t % 2] = h[p + (W - t) up] for t = 0 .. T - 1, r = 0 .. up - 1, p = (r down) mod up, zero where |p + (W - t) up| > K,
+ * so that output m, m down = j0 up + p, reads column r = m mod up downwards against y[j0 - W + t], two taps a step, and the threads of consecutive
+ * outputs read consecutive pairs (syntalker_amd.audio.pack_taps makes it from the natural-order table).  A table size that is not a whole number of
+ * pair rows, n_taps = 2 up (W + 1), is refused.
+ *
+ * The call enqueues on `stream`, allocates nothing and uses no atomics.  It writes exactly ceil(n_i up / down) values per take from out_off[i] on and
+ * nothing else; a take's bits do not depend on what shares the call; every index that grows with the take is 64-bit (m down passes 2^31 within
+ * seconds of audio).  Refused before any launch, non-zero with syn_last_error naming the function: a null pointer (y, the offsets, taps, or both
+ * outputs), n_takes outside 1 .. 65535, up or down < 1, gcd(up, down) != 1, a negative or ill-shaped n_taps, a misaligned taps or out64. */
+int syn_audio_resample(const float* y, const int64_t* sample_off, const int64_t* out_off, int32_t n_takes, int64_t max_samples, int32_t up, int32_t down,
+                       const double* taps, int64_t n_taps, float* out32, double* out64, void* stream);
+
 /* Baseline JPEG of device frames (additive, SYN_ABI_VERSION stays 9; csrc/syn_jpeg.inc): what the reference's utils/media.py hands to
  * ffmpeg frame by frame is encoded where syn_render_shade left it, so that a picture crosses to the host as a file of a fiftieth of its size.  Every
  * call enqueues on `stream`, allocates nothing and uses no atomics.  Nothing is floating point: a frame's bytes are those of the numpy restatement

@@ -2,7 +2,7 @@
 """L1 diversity and beat consistency of a results directory as the reference's `test()` writes it (diffusion_rvqvae_trainer.py:702-709:
 `res_<id>.npz` with `poses` (n, 165) SMPL-X axis-angle, `trans`, `betas`), the way `test()` computes them (:626-638, 668, 677-684, 722-728).
 
-    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR | --waves DIR] [--face]
+    python scripts/motion_metrics_from_results.py RESULTS_DIR --smplx-model SMPLX_NEUTRAL_2020.npz --mean-vel mean_vel_smplxflame_30.npy [--onsets DIR | --waves DIR [--resample]] [--face]
 
 Per take: rest joints and the hands' mean pose from the model file and the take's betas (joints.smplx_rest_joints, host), the 55 skeleton joints by
 forward kinematics on the device with zero transl as `test()` passes it (joints.smplx_joints; the hand mean pose is added to the hand joints'
@@ -13,7 +13,8 @@ consistency of the slice [mask, n - mask) against the take's audio onsets (with 
              librosa.onset.onset_detect); a take without its file, or with no onsets, is left out of `bc` (named on stderr)
 --waves      a directory with `<id>.wav` (or `<id>.npy`): the take's waveform at --audio-sr (16000: the reference's wave16k/), from which the onsets are
              detected as test() does (:681-683; metrics.beat_consistency_from_audio, syntalker_amd.audio - no librosa).  A file at another rate is
-             refused: resampling is out of scope.  --onsets and --waves together are an error; with neither there is no `bc`
+             refused: resampling is out of scope - unless --resample is given.  --onsets and --waves together are an error; with neither there is no `bc`
+--resample   with --waves: a `.wav` at any rate is brought to --audio-sr on the device first (syntalker_amd.audio.load_wave)
 --flat-hand-mean   for results made with a model built with flat_hand_mean=True: no hand mean pose is added
 --face       also test()'s `l2 loss` and `lvel loss` (:640-675, :713-714): the face meshes of `res_<id>.npz` against `gt_<id>.npz` (jaw pose and
              `expressions` of each, everything else zero; metrics.face_losses), accumulated as test() does: sum(value x n) / frames
@@ -46,6 +47,7 @@ def main(argv=None):
     ap.add_argument("--onsets")
     ap.add_argument("--waves")
     ap.add_argument("--audio-sr", type=int, default=16000)
+    ap.add_argument("--resample", action="store_true")
     ap.add_argument("--flat-hand-mean", action="store_true")
     ap.add_argument("--face", action="store_true")
     ap.add_argument("--mask", type=int, default=60)
@@ -54,6 +56,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.onsets is not None and a.waves is not None:
         ap.error("--onsets and --waves exclude each other: the onsets are read, or detected from the waveforms")
+    if a.resample and a.waves is None:
+        ap.error("--resample applies to the files of --waves")
     ids = read_ids(a.results_dir)
     if not ids:
         raise SystemExit(f"motion_metrics_from_results: no res_<id>.npz in {a.results_dir}")
@@ -84,7 +88,8 @@ def main(argv=None):
             path = next((p for p in (os.path.join(a.waves, f"{i}.wav"), os.path.join(a.waves, f"{i}.npy")) if os.path.exists(p)), None)
             onsets = np.zeros(0)
             if path is not None and n > 2 * a.mask:
-                short = metrics.audio_slice_of_test(audio.read_wave(path, a.audio_sr), n, a.mask, a.audio_sr, 30.0)
+                wave = audio.load_wave(path, a.audio_sr) if a.resample else audio.read_wave(path, a.audio_sr)
+                short = metrics.audio_slice_of_test(wave, n, a.mask, a.audio_sr, 30.0)
                 onsets = audio.onset_detect(short, sr=a.audio_sr, hop_length=512, units="time") if len(short) else onsets
         else:
             path = os.path.join(a.onsets, f"{i}.npy")

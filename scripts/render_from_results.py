@@ -15,7 +15,7 @@ take is printed.  Prints one JSON line: {"takes", "frames", "width", "height", "
 --format avi       one playable file per take instead of frames: `video_<id>.avi`, Motion-JPEG encoded on the device (syntalker_amd/video.py, JPEG --quality
                    Q), and with --waves WAVE_DIR the take's `<id>.wav` (any rate, int16 or float, first channel) as its PCM sound track at its own rate,
                    cut at the video's end.  The video runs at 30 / max(1, int(30 // fps)) frames a second, the rate the drawn frames have in the take.
-                   No frame files and no ffmpeg line; the JSON line gains "videos".  Resampling stays out.
+                   No frame files and no ffmpeg line; the JSON line gains "videos".  The track is not resampled.
 --flat-hand-mean   for results made with a model built with flat_hand_mean=True
 """
 import argparse

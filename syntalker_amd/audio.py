@@ -8,8 +8,9 @@ fp64 on the device, in a fixed order: a take's result does not depend on what sh
 
 Differences to librosa, on purpose:
 * `onset_strength` returns float64 (librosa: float32 - its spectrogram is complex64).  The onsets are decisions on the float64 envelope.
-* no resampling: the input IS the waveform at `sr` (the reference's `librosa.load` takes a file to 22.05 kHz and `librosa.resample` brings it back to
-  16 kHz; feed the 16 kHz waveform).  `read_wave` refuses a file of another rate.
+* the feature functions do not resample: their input IS the waveform at `sr`, and `read_wave` refuses a file of another rate.  A file at any other
+  rate goes through `load_wave` / `resample` first (csrc/syn_audio_resample.inc): the reference's `librosa.load` + `librosa.resample`
+  restated as a Kaiser-windowed sinc on the exact rational grid, fp64 behind the fp32 samples - the project's own definition, not soxr's bits.
 
 Every function takes a numpy array, a CPU tensor or a device tensor (arrays and CPU tensors are copied to the current device), or a list of takes of
 different lengths, which is ONE batched launch sequence and returns a list.  Arguments are checked (ValueError) before anything touches the device.
@@ -260,17 +261,164 @@ def onset_amplitude(y, sr=16000):
 
 def read_wave(path, sr=16000):
     """A `.wav` (scipy.io.wavfile: int16 -> / 32768, float as it is; the first channel of several) or `.npy` waveform as float32.  A `.wav` at another
-    rate than `sr` is refused: resampling is out of scope, bring the 16 kHz waveform the reference's `wave16k/` holds."""
+    rate than `sr` is refused: resampling is out of scope here, bring the 16 kHz waveform the reference's `wave16k/` holds - or use `load_wave`."""
     if str(path).endswith(".npy"):
         y = np.load(path)
     else:
         from scipy.io import wavfile
         rate, y = wavfile.read(path)
         if rate != sr:
-            raise ValueError(f"{path}: sample rate {rate}, expected {sr}; resampling is out of scope - convert the file to {sr} Hz first")
+            raise ValueError(f"{path}: sample rate {rate}, expected {sr}; resampling is out of scope - convert the file to {sr} Hz first, or use load_wave")
         if y.dtype == np.int16:
             y = y.astype(np.float32) / 32768.0
         elif y.dtype.kind != "f":
             raise ValueError(f"{path}: int16 or float samples, got {y.dtype}")
     y = np.asarray(y, dtype=np.float32)
     return np.ascontiguousarray(y[:, 0] if y.ndim == 2 else y)
+
+
+# ---- resampling (csrc/syn_audio_resample.inc, DESIGN.md 25) -------------------------------------------------------------------------------------------
+RESAMPLE_ZEROS = 64                          # zero crossings of the sinc on either side
+RESAMPLE_ROLLOFF = 0.9475937167399596        # the pass band's edge as a fraction of the lower Nyquist rate
+RESAMPLE_BETA = 14.769656459379492           # of the Kaiser window
+RESAMPLE_MAX_TAPS = 1 << 22                  # 2 K + 1 may not exceed this
+
+
+def _check_rates(orig_sr, target_sr, what):
+    for name, sr in (("orig_sr", orig_sr), ("target_sr", target_sr)):
+        if isinstance(sr, bool) or not isinstance(sr, (int, float, np.integer, np.floating)) or not sr > 0 or int(sr) != sr or sr >= 2 ** 31:
+            raise ValueError(f"{what}: {name} must be a positive integer number of Hz, got {sr!r}")
+    return int(orig_sr), int(target_sr)
+
+
+_taps_cache = {}
+
+
+def resample_taps(orig_sr, target_sr):
+    """(L, M, K, h) of the conversion orig_sr -> target_sr: L / M = target_sr / orig_sr in lowest terms, h the 2 K + 1 taps h[-K .. K] (float64 numpy,
+    read-only, natural order: h[K + k]) of g sinc(g k / L) I0(beta sqrt(1 - u^2)) / I0(beta), u = g k / (64 L), g = rolloff min(1, L / M),
+    K = floor(64 L / g).  Built once per (L, M) on the host.  A table of more than 2^22 taps is a ValueError naming both rates."""
+    import math
+    orig_sr, target_sr = _check_rates(orig_sr, target_sr, "resample_taps")
+    d = math.gcd(orig_sr, target_sr)
+    L, M = target_sr // d, orig_sr // d
+    if (L, M) not in _taps_cache:
+        g = RESAMPLE_ROLLOFF * min(1, L / M)
+        K = int(math.floor(RESAMPLE_ZEROS * L / g))
+        if 2 * K + 1 > RESAMPLE_MAX_TAPS:
+            raise ValueError(f"resample: {orig_sr} Hz -> {target_sr} Hz needs a table of {2 * K + 1} taps (L = {L}, M = {M}), more than {RESAMPLE_MAX_TAPS}: "
+                             "choose rates with a larger common divisor")
+        k = np.arange(-K, K + 1, dtype=np.float64)
+        u = g * k / (L * RESAMPLE_ZEROS)
+        h = g * np.sinc(g * k / L) * np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(0.0, 1.0 - u * u))) / np.i0(RESAMPLE_BETA)
+        h.setflags(write=False)
+        _taps_cache[(L, M)] = (L, M, K, h)
+    return _taps_cache[(L, M)]
+
+
+def pack_taps(L, M, K, h):
+    """The kernel's layout of the table (include/syn_hip.h): (T / 2, L, 2) float64, T = 2 (K // L) + 2, entry [t // 2, r, t % 2] = h[p + (W - t) L]
+    with W = K // L and p = (r M) mod L the phase of the outputs m = r (mod L); zero where the index leaves -K .. K."""
+    W = K // L
+    p = (np.arange(L, dtype=np.int64) * M) % L
+    k = p[None, :] + (W - np.arange(2 * W + 2, dtype=np.int64)[:, None]) * L          # [t, r]
+    inside = np.abs(k) <= K
+    table = np.where(inside, h[np.where(inside, k + K, 0)], 0.0)
+    return np.ascontiguousarray(table.reshape(W + 1, 2, L).transpose(0, 2, 1))
+
+
+_device_taps_cache = {}
+
+
+def _device_taps(L, M, K, h, dev):
+    import torch
+    key = (L, M, str(dev))
+    if key not in _device_taps_cache:
+        if len(_device_taps_cache) >= 8:                # a handful of ratios at most stay resident (a table is 0.5 MB at 320 / 441, 24 MB at L = 16001)
+            _device_taps_cache.pop(next(iter(_device_taps_cache)))
+        _device_taps_cache[key] = torch.from_numpy(pack_taps(L, M, K, h)).to(dev)
+    return _device_taps_cache[key]
+
+
+def resample_length(n, L, M):
+    return -((-n * L) // M)
+
+
+def resample(y, orig_sr, target_sr, dtype=None):
+    """The take(s) at `orig_sr` brought to `target_sr`: ceil(n L / M) samples each, on the device, y[m] = sum_j x[j] h[m M - j L] with the taps of
+    `resample_taps` - every sum an fp64 fma chain over ascending j, rounded once to float32 (`dtype=torch.float64`: the sums themselves).  One launch
+    for a list of takes; a take's bits do not depend on its batch mates.  `orig_sr == target_sr` returns what it was given, without a launch."""
+    import torch
+    from . import _lib
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"resample: dtype is torch.float32 or torch.float64, got {dtype!r}")
+    orig_sr, target_sr = _check_rates(orig_sr, target_sr, "resample")
+    takes, many = _as_list(y)
+    _check_takes(takes, "resample", 1)
+    if orig_sr == target_sr:
+        return y
+    L, M, K, h = resample_taps(orig_sr, target_sr)
+    b = _Batch(takes)
+    taps = _device_taps(L, M, K, h, b.dev)
+    lens = [resample_length(n, L, M) for n in b.lens]
+    ooff_host = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ooff = torch.from_numpy(ooff_host).to(b.dev)
+    out = torch.empty(int(ooff_host[-1]), dtype=dtype, device=b.dev)
+    _lib.check(_lib.load().syn_audio_resample(b.y.data_ptr(), b.soff.data_ptr(), ooff.data_ptr(), len(b.lens), max(b.lens), L, M, taps.data_ptr(), taps.numel(),
+                                              out.data_ptr() if dtype == torch.float32 else None, out.data_ptr() if dtype == torch.float64 else None,
+                                              _lib.current_stream(b.dev)), "syn_audio_resample")
+    parts = [out[ooff_host[i]:ooff_host[i + 1]] for i in range(len(lens))]
+    return parts if many else parts[0]
+
+
+def decode_wave(path):
+    """(rate, samples) of a `.wav` as scipy.io.wavfile reads it: float32 samples, the first channel of several; int16 / 2^15, int32 / 2^31 (24-bit
+    files arrive as int32), uint8 (v - 128) / 128, float as it is."""
+    from scipy.io import wavfile
+    rate, y = wavfile.read(path)
+    if y.dtype == np.int16:
+        y = y.astype(np.float32) / 32768.0
+    elif y.dtype == np.int32:
+        y = (y.astype(np.float64) / 2147483648.0).astype(np.float32)
+    elif y.dtype == np.uint8:
+        y = (y.astype(np.float32) - 128.0) / 128.0
+    elif y.dtype.kind != "f":
+        raise ValueError(f"{path}: int16, int32, uint8 or float samples, got {y.dtype}")
+    y = np.asarray(y, dtype=np.float32)
+    return int(rate), np.ascontiguousarray(y[:, 0] if y.ndim == 2 else y)
+
+
+def load_waves(paths, sr=16000, via=None):
+    """`load_wave` of several files: the files of one rate share one `resample` launch (per step), and come back in the order given."""
+    import torch
+    orig = []
+    for path in paths:
+        if str(path).endswith(".npy"):
+            y = np.asarray(np.load(path), dtype=np.float32)
+            orig.append((int(sr), np.ascontiguousarray(y[:, 0] if y.ndim == 2 else y)))
+        else:
+            orig.append(decode_wave(path))
+    if via is not None:
+        _check_rates(via, sr, "load_wave (via)")
+    out = [None] * len(orig)
+    for rate in sorted({r for r, _ in orig}):
+        idx = [i for i, (r, _) in enumerate(orig) if r == rate]
+        waves = [orig[i][1] for i in idx]
+        for w, path in zip(waves, (paths[i] for i in idx)):
+            if w.ndim != 1 or len(w) < 1:
+                raise ValueError(f"{path}: no samples")
+        if rate != sr:
+            steps = [(rate, sr)] if via is None else [(rate, int(via)), (int(via), sr)]
+            for a, b in steps:
+                waves = resample(waves, a, b)
+        for i, w in zip(idx, waves):
+            out[i] = _to_device(w, torch.float32)
+    return out
+
+
+def load_wave(path, sr=16000, via=None):
+    """A `.wav` at ANY rate (or a `.npy` waveform, taken to be at `sr`) as a float32 DEVICE tensor at `sr`: decoded like `read_wave` (plus int32 and
+    uint8 PCM) and, where the file's rate differs, resampled in one step (`resample`).  `via=22050` runs the reference's own two steps instead
+    (librosa.load's 22.05 kHz, then librosa.resample to `sr`).  mp3 and flac are not decoded."""
+    return load_waves([path], sr, via)[0]

@@ -1806,6 +1806,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_mesh.inc"
 #include "syn_render.inc"
 #include "syn_audio.inc"
+#include "syn_audio_resample.inc"
 #include "syn_jpeg.inc"
 
 namespace {

@@ -8,7 +8,7 @@ set of rest joints per subject: `smplx_rest_joints` is that one host product (nu
 default, and what the reference's `smplx.create(..., use_pca=False)` gives - adds the hands' mean pose to the axis-angle vector of the 30 hand
 joints (`full_pose += pose_mean`); `smplx_rest_joints` reads it from the model file (`hands_meanl` / `hands_meanr`) into `Skeleton.pose_mean`.
 The vertices and the face losses are `syntalker_amd/mesh.py` (which runs `syn_fk_joints`' kernel for its joint transforms); the pictures are
-`syntalker_amd/render.py`, the video with its sound track (Motion-JPEG AVI, PCM) `syntalker_amd/video.py`; H.264 / mp4 and audio resampling stay out.  Device tensors only, like the rest of the package: a CPU tensor or a missing library raises."""
+`syntalker_amd/render.py`, the video with its sound track (Motion-JPEG AVI, PCM) `syntalker_amd/video.py`, audio resampling `syntalker_amd/audio.py`; H.264 / mp4 stay out.  Device tensors only, like the rest of the package: a CPU tensor or a missing library raises."""
 from __future__ import annotations
 
 import numpy as np

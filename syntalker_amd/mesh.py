@@ -10,7 +10,7 @@ DESIGN.md §21).  `smplx` is not imported; the algebra is linear blend skinning:
 `smplx_mesh` does the per-subject part once on the host in fp64 (as `joints.smplx_rest_joints` does); `smplx_vertices` runs the per-frame part in two
 launches, `syn_fk_transforms` and `syn_mesh_vertices`.  The first 55 joints come along; the other 72 entries of `smplx(...)["joints"]` (vertex-selected
 joints, face landmarks) stay out.  Drawing the vertices is `syntalker_amd/render.py`, the video with its sound track (Motion-JPEG AVI, PCM)
-`syntalker_amd/video.py`; H.264 / mp4 and audio resampling stay out.  Device tensors only, like the rest of the package: a CPU tensor or a missing library raises."""
+`syntalker_amd/video.py`, audio resampling `syntalker_amd/audio.py`; H.264 / mp4 stay out.  Device tensors only, like the rest of the package: a CPU tensor or a missing library raises."""
 from __future__ import annotations
 
 import numpy as np

@@ -10,7 +10,8 @@ What is the reference's: camera and light poses, `ymag`, the colour, the panel l
 type.  What is this project's own: the 1/16-pixel grid, and the tone - `base * min(1, ambient + diffuse * max(0, n . l))` is a Lambert term, NOT
 pyrender's metallic-roughness shader, and will not match it pixel for pixel.  Coverage and depth follow the reference's camera; tone does not.  The
 pixel mapping of the orthographic camera (ymag spans half the height, square pixels) is recalled from pyrender, not checked against it: pyrender is
-not installed here.  The frames become a video with sound in syntalker_amd/video.py (Motion-JPEG AVI, PCM); H.264 / mp4 and resampling stay out.
+not installed here.  The frames become a video with sound in syntalker_amd/video.py (Motion-JPEG AVI, PCM); H.264 / mp4 stay out, audio
+resampling is syntalker_amd/audio.py (`load_wave`).
 
 Device tensors only, like the rest of the package: a CPU tensor or a missing library raises `SynHipError`."""
 from __future__ import annotations

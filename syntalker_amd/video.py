@@ -1,6 +1,7 @@
 """The takes as video with sound: a baseline JPEG encoder on the device (csrc/syn_jpeg.inc) and a Motion-JPEG AVI writer with a PCM
 sound track on the host - what the reference gets from ffmpeg in `utils/media.py` (`convert_img_to_mp4`, `add_audio_to_video`), as one playable
-file per take and without any library.  H.264 / mp4, audio resampling and OpenDML (files past 2 GB) stay out.
+file per take and without any library.  H.264 / mp4 and OpenDML (files past 2 GB) stay out; the sound track is written
+at its own rate (bringing a file to another rate is `syntalker_amd.audio.load_wave`).
 
 The frames `render.render` left on the device are encoded there, by integer rules stated in include/syn_hip.h and restated in tests/jpeg_ref.py
 (JFIF colour in 16-bit fixed point, 4:2:0, a 13-bit integer DCT, the Annex K tables scaled by the IJG quality rule, one restart interval per MCU
