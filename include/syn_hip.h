@@ -350,6 +350,45 @@ int syn_render_shade(const int32_t* face_id, const int32_t* xy_sub, const float*
                      int32_t n_faces, int32_t width, int32_t height, float light_x, float light_y, float light_z, float base_r, float base_g, float base_b,
                      float ambient, float diffuse, int32_t background_r, int32_t background_g, int32_t background_b, uint8_t* rgb, void* stream);
 
+/* Stick figures of h3d takes: the scene of the reference's utils/plot_script.py:86-177 (one perspective camera, a translucent ground rectangle, the
+ * root's past trajectory, 5 or 15 polylines) as a rasteriser of thick lines (additive, SYN_ABI_VERSION stays 9; csrc/syn_plot.inc).  Every
+ * call enqueues on `stream`, allocates nothing, is graph-capturable, deterministic and uses no atomics of any kind; a frame's output depends on the
+ * take's trajectory, that frame's joints and its index alone.  size: 1 .. 4096 pixels a side, row 0 on top.  Positions are in units of 1/16 pixel.
+ *
+ * syn_plot_setup: data (n_frames, n_joints, 3) the prepared joints of the frames to draw, trajec (n_take, 2) the whole take's root (x, z), index
+ * (n_frames) int32 on the device: each frame's position in the take (outside [0, n_take): no ground, no trajectory), bounds {min x, max x, min z,
+ * max z} of the take, segments (n_segments, 4) int32 {joint a, joint b, layer >= 2, half-width R} with layers ascending, camera 22 doubles: the 4 x 4 projection M row by row,
+ * then the 2 x 3 map A from projected (u, v) to pixel (col, row).  n_slots >= n_segments + max(0, max index - 1).  It writes into the workspace
+ *   records (n_frames, n_slots, 8) int32  {ax, ay, bx, by, T, R | layer << 16, x0 | x1 << 16, y0 | y1 << 16} per slot, in paint order: the frame's
+ *                                         max(0, index - 1) trajectory segments trajec[k] - trajec[index] -> trajec[k + 1] - trajec[index] on y = 0
+ *                                         (fp32 differences; layer 1, half-width traj_half_width), then the chain segments in table order; every
+ *                                         other slot, and a dropped segment, is {0, 0, 0, 0, -1, 0, 1, 1} (x0 > x1: no pixel)
+ *   grounds (n_frames, 24) int32          {corners n, slots of the frame, x0 | x1 << 16, y0 | y1 << 16, n x (x, y), zeros}: the quad [min x - tx, max x -
+ *                                         tx] x [min z - tz, max z - tz] on y = 0 ((tx, tz) = trajec[index], fp32 differences), n = 0 when nothing is left
+ * A point p becomes clip = M p, each used row (0, 1, 3) summed as ((m0 x + m1 y) + m2 z) + m3, then (u, v) = (clip.x / clip.w, clip.y / clip.w), col =
+ * (a00 u + a01 v) + a02, row = (a10 u + a11 v) + a12, and is snapped to rint(16 col), rint(16 row): fp64, every operation rounded on its own.  A
+ * segment with an end that is not finite, with R outside [1, min(4095, 16 size)] or a joint outside [0, n_joints) is dropped.  A segment that crosses
+ * w = 1/16 is cut there (the end behind becomes in + t (out - in), t = (in.w - 1/16) / (in.w - out.w), w = 1/16); wholly behind, it is dropped.  A
+ * segment with a snapped end more than 16 size units (one image side: the guard band) beyond a border is dropped whole.  T = isqrt(R^2 |b - a|^2), the
+ * exact integer root; -1 for a segment of zero length (a disc).  The pixel box holds every pixel with a sample in [min - R, max + R], clipped to the
+ * image.  The ground is clipped, not dropped: in clip space against w >= 1/16, then in pixels against the four sides of the guard band (corner = in + t
+ * (out - in), t = (bound - in.c) / (out.c - in.c), the clipped coordinate set to the bound), snapped, clamped to the band, consecutive duplicates
+ * removed and oriented to a positive doubled area: up to 9 corners.
+ * syn_plot_draw: -> rgb (n_frames, size, size, 3) bytes from the same workspace.  Pixel (i, j) has 16 samples (16 i + 2 + 4 u, 16 j + 2 + 4 v), u, v = 0 .. 3.
+ * A segment a-b covers a sample s when 0 <= (s - a).(b - a) <= |b - a|^2 and |(b - a) x (s - a)| <= T, or |s - a|^2 <= R^2, or |s - b|^2 <= R^2 (a capsule:
+ * round caps and joins), all in int64.  A layer's 16-bit mask is the OR over its segments; with k = popcount(mask) a line layer paints c = (c (16 - k) +
+ * colour k + 8) >> 4 per channel.  The ground covers a sample when every edge value E_ab(s) = (bx - ax)(sy - ay) - (by - ay)(sx - ax) is > 0, or = 0 on a
+ * top (dy = 0, dx > 0) or left (dy < 0) edge, and paints c = (c (32 - k) + 128 k + 16) >> 5.  White, then the ground, then the layers in ascending
+ * order.  colours (n_layers) int32 r | g << 8 | b << 16 per layer (entry 0, the ground's, is not read); a record whose layer is outside [1, n_layers)
+ * is skipped.  workspace: syn_plot_workspace_bytes(n_frames, n_slots) = 32 n_frames n_slots + 96 n_frames bytes (-1 for counts below 1), 16-byte
+ * aligned, as is the segment table. */
+int64_t syn_plot_workspace_bytes(int64_t n_frames, int32_t n_slots);
+int syn_plot_setup(const float* data, int64_t n_frames, int32_t n_joints, const float* trajec, int64_t n_take, const int32_t* index, const float* bounds,
+                   const int32_t* segments, int32_t n_segments, const double* camera, int32_t size, int32_t traj_half_width, int32_t n_slots,
+                   void* workspace, void* stream);
+int syn_plot_draw(const void* workspace, int64_t n_frames, int32_t n_slots, const int32_t* colours, int32_t n_layers, int32_t size, uint8_t* rgb,
+                  void* stream);
+
 /* The audio front end: amplitude envelope and onset detection of 16 kHz waveforms (additive, SYN_ABI_VERSION stays 9; csrc/syn_audio.inc) -
  * what dataloaders/beat_sep_lower.py:391-409 and utils/metric.py:64-76 take from numpy stride tricks and librosa.onset.onset_detect.  Several takes of
  * different lengths share a call: y [total samples] fp32 is the takes back to back, sample_off and frame_off [n_takes + 1] int64 ON THE DEVICE are

@@ -1805,6 +1805,7 @@ int launch_stack(const SArgs& a, int mt, hipStream_t s) {
 #include "syn_joints.inc"
 #include "syn_mesh.inc"
 #include "syn_render.inc"
+#include "syn_plot.inc"
 #include "syn_audio.inc"
 #include "syn_audio_resample.inc"
 #include "syn_jpeg.inc"
