@@ -844,6 +844,17 @@ typedef struct syn_wavenc {
 } syn_wavenc;
 int32_t syn_wav_out_frames(int32_t n_samples);
 int64_t syn_wav_workspace_bytes(int32_t n_clips, int32_t n_samples);
+/* Where a clip's intermediates lie in the workspace (additive, SYN_ABI_VERSION stays 9; host only: no launch, no GPU needed) - the plan syn_wav_encode
+ * itself runs from, for tests and tools that read the layers back.  Clip i starts at bf16 element i * per_clip.  out[SYN_WAV_LAYOUT_WORDS], in order:
+ *   L1 L2 L3 L4          positions after blocks 0, 1 (= 2), 3 (= 4), 5 (L4 = syn_wav_out_frames)
+ *   per_clip             bf16 elements of a clip's workspace (x 2 x n_clips = syn_wav_workspace_bytes)
+ *   x1 z1 s1 x2 z2 x3 z3 s3 x4 z4 x5 z5 s5     bf16-element offsets inside a clip: x = a block's input, z = its conv1 output, s = its shortcut conv;
+ *                        channels-last rows of 64 (x1 .. x3), 128 (z3 .. x5) or 256 (z5, s5) channels
+ *   halo slack           zero rows in front of and behind the tensors a padded convolution reads (z1, x2, z2, z3, x4, z4, z5: row 0 of the data is
+ *                        row `halo` of the region), zero rows behind those and behind the tensors a strided convolution reads in row groups (x1, x3, x5)
+ * Non-zero with a syn_last_error message for out = NULL or n_samples < 15. */
+#define SYN_WAV_LAYOUT_WORDS 20
+int syn_wav_layout(int32_t n_samples, int64_t* out);
 int syn_wav_encode(const syn_wavenc* enc, const float* wav, int32_t n_clips, int32_t n_samples, void* workspace, float* out,
                    void* stream);
 

@@ -1565,6 +1565,17 @@ int64_t syn_wav_workspace_bytes(int32_t n_clips, int32_t n_samples) {
     return (int64_t)wav_plan(n_samples).per_clip * n_clips * 2;
 }
 
+// Where syn_wav_encode keeps what inside a clip's workspace (host only, no launch): the WavPlan it runs from, word for word.
+int syn_wav_layout(int32_t n_samples, int64_t* out) {
+    if (!out) return fail_msg("syn_wav_layout: null argument");
+    if (n_samples < 15) return fail_msg("syn_wav_layout: clip too short");
+    const WavPlan p = wav_plan(n_samples);
+    const int64_t words[] = {p.L1, p.L2, p.L3, p.L4, p.per_clip, p.x1, p.z1, p.s1, p.x2, p.z2, p.x3, p.z3, p.s3, p.x4, p.z4, p.x5, p.z5, p.s5, kHalo, kSlack};
+    static_assert(sizeof(words) == SYN_WAV_LAYOUT_WORDS * sizeof(int64_t), "include/syn_hip.h: SYN_WAV_LAYOUT_WORDS");
+    memcpy(out, words, sizeof(words));
+    return 0;
+}
+
 int syn_wav_encode(const syn_wavenc* enc, const float* wav_in, int32_t n_clips, int32_t n_samples, void* workspace, float* out,
                    void* stream) {
     if (!enc || !wav_in || !workspace || !out || n_clips <= 0) return fail_msg("syn_wav_encode: null argument");

@@ -46,10 +46,21 @@ def _model(dim):
     dict(cin=512, cout=512, taps=1, stride=1, dil=1, pad=0, up=0, t=16, relu_in=1, relu_out=0, resid=1),
     dict(cin=512, cout=512, taps=3, stride=1, dil=1, pad=1, up=1, t=20, relu_in=0, relu_out=0),
     dict(cin=512, cout=256, taps=3, stride=1, dil=1, pad=1, up=0, t=100, relu_in=0, relu_out=0, valid=180),
+    # edges: a single position; one past the 32-position tile; the stride-2 geometry at odd lengths (one tile, and one position into a third);
+    # every tap but the centre in the padding; the upsampled read of a single row
+    dict(cin=96, cout=128, taps=3, stride=1, dil=1, pad=1, up=0, t=1, relu_in=0, relu_out=1),
+    dict(cin=96, cout=128, taps=3, stride=1, dil=1, pad=1, up=0, t=33, relu_in=0, relu_out=1),
+    dict(cin=512, cout=512, taps=4, stride=2, dil=1, pad=1, up=0, t=33, relu_in=0, relu_out=0),
+    dict(cin=512, cout=512, taps=4, stride=2, dil=1, pad=1, up=0, t=131, relu_in=0, relu_out=0),
+    dict(cin=512, cout=512, taps=3, stride=1, dil=9, pad=9, up=0, t=5, relu_in=1, relu_out=0),
+    dict(cin=512, cout=512, taps=3, stride=1, dil=1, pad=1, up=1, t=1, relu_in=0, relu_out=0),
 ])
 def test_conv1d_kernel_vs_torch(cfg):
     """One launch of the generic Conv1d kernel against F.conv1d on the same bf16-rounded operands (fp32 accumulate both
-    sides: agreement to accumulation-order round-off), for every geometry the encoder / decoder uses + ragged lengths."""
+    sides: agreement to accumulation-order round-off), for every geometry the encoder / decoder uses + ragged lengths.
+    Beside the norms, every element of the fp32 output against the float64 convolution: |got - want| <= c 2^-24 conv(|w|, |x|), c = 2 (K / 32 + 4)
+    for the K / 32 = taps x cin / 32 MFMA steps behind an output, one fp32 rounding each, then the bias, the residual and the store - doubled because
+    the matrix pipe's rounding inside a step is not documented."""
     g = torch.Generator().manual_seed(5)
     n, t, cin, cout = 3, cfg["t"], cfg["cin"], cfg["cout"]
     valid = cfg.get("valid", cout)
@@ -84,6 +95,17 @@ def test_conv1d_kernel_vs_torch(cfg):
     assert torch.isfinite(yf).all()
     assert rel_l2(yf, want) < 2e-5
     assert rel_l2(yb[..., :valid].float(), want) < 4e-3
+    want64 = F.conv1d(xin.double(), w.double(), b.double(), stride=cfg["stride"], padding=cfg["pad"], dilation=cfg["dil"]).permute(0, 2, 1)
+    if resid is not None:
+        want64 = want64 + resid.double()
+    if cfg["relu_out"]:
+        want64 = F.relu(want64)
+    assert want64.shape == (n, t_out, valid)
+    s = F.conv1d(xin.double().abs(), w.double().abs(), None, stride=cfg["stride"], padding=cfg["pad"], dilation=cfg["dil"]).permute(0, 2, 1)
+    c = 2.0 * (cfg["taps"] * cin // 32 + 4)
+    ratio = (yf.cpu().double() - want64).abs() / (2.0 ** -24 * s).clamp_min(1e-300)
+    print(f"conv1d {cfg}: max |got - want| / (2^-24 conv(|w|, |x|)) = {float(ratio.max()):.2f}, c = {c:.0f}")
+    assert float(ratio.max()) <= c
 
 
 @pytest.mark.parametrize("part,dim", PARTS)
